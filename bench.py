@@ -1,6 +1,20 @@
 """Benchmark: device-resident batched PacketParser::parse on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--packets P]
+                    [--full] [--dump-outputs DIR]
+
+A plain run does what the headline needs and no more: it generates the batch,
+parses it once with the descriptor check, warms up, times --steps launches,
+writes its outputs if --dump-outputs is given and prints the JSON line. --full
+adds the legs listed under "Reported next to the GPU number" below.
+
+--dump-outputs DIR writes what the last timed step left in the records / ext
+tensors, as rank 0's caller of parse_batch would read them: a fixed seeded
+sample of DUMP_FRAMES frames (every frame of a smaller batch), float32 .npy
+files holding the byte values (frame_index.npy float64, records.npy [m, 8],
+ext.npy [2, m, 16] with the chain entries no record flags zeroed: the ABI
+leaves those unspecified). The generator is seeded, so the same arguments
+give the same frames and the same sample in every run and build.
 
 One step = one zp_parse_batch_device launch over the whole per-GPU batch
 (inputs already resident in HBM). Default workload: BASELINE config 3 — 16M
@@ -19,9 +33,12 @@ JSON line. Under a launcher, --gpus must equal WORLD_SIZE.
 split into N contiguous shards, rank r parsing the r-th (strong scaling; at
 N = 1 the whole 95 GB batch on one GPU).
 
-Reported next to the GPU number:
+Reported in every line:
   roofline      algorithmic bytes (sum of frame lengths) / mean kernel time
                 from HIP events on the launch stream, vs 8.0 TB/s HBM peak
+
+Reported next to the GPU number with --full (--no-cpu, --no-pcie and --no-c5
+take single legs out again):
   cpu_baseline  the CPU oracle (a C port of the reference; the Rust original
                 cannot be built here) on a bounded sample of the same frames
                 (rank 0 at N = 1 only)
@@ -66,6 +83,8 @@ WORKLOADS = {
 DEFAULT_PACKETS = {"c1": 1 << 20, "c2": 1 << 20, "c3": 1 << 24, "c4": 1 << 24,
                    "c6": 1 << 24}
 C5_TOTAL = 1 << 28          # config 5: one 256M-frame stream over all ranks
+DUMP_FRAMES = 1 << 18       # --dump-outputs: frames sampled from a larger batch
+DUMP_SEED = 0x5EED2025
 
 
 def log(*a):
@@ -279,6 +298,39 @@ def gather_rows(row, world, rank, dev):
     return t.cpu().numpy()
 
 
+def dump_sample(n):
+    """Sorted indices of the frames --dump-outputs writes: all n, or a fixed
+    seeded sample of DUMP_FRAMES of them."""
+    if n <= DUMP_FRAMES:
+        return np.arange(n, dtype=np.int64)
+    rng = np.random.default_rng(DUMP_SEED)
+    return np.sort(rng.choice(n, DUMP_FRAMES, replace=False)).astype(np.int64)
+
+
+def dump_outputs(zp, path, records, ext):
+    """Writes the sampled frames' records and extension chains, as
+    records_to_numpy hands them to a caller, under `path`: frame_index.npy
+    (float64 [m]), records.npy (float32 [m, 8], the record bytes) and ext.npy
+    (float32 [2, m, 16], the entry bytes; entries whose record flags no chain
+    are unspecified by the ABI and written as zeros). 42 MiB at DUMP_FRAMES."""
+    torch.cuda.synchronize()
+    idx = dump_sample(records.shape[0])
+    sel = torch.from_numpy(idx).to(records.device)
+    rec, chains = zp.batch.records_to_numpy(records[sel], ext[:, sel])
+    flags = zp.records.unpack(rec)["flags"]
+    e = np.ascontiguousarray(chains).view(np.uint8).reshape(2, -1, zp.records.EXT_BYTES).copy()
+    e[0][(flags & zp.records.F_EXT) == 0] = 0
+    e[1][(flags & zp.records.F_INNER_EXT) == 0] = 0
+    r = np.ascontiguousarray(rec).view(np.uint8).reshape(-1, zp.records.RECORD_BYTES)
+    os.makedirs(path, exist_ok=True)
+    arrays = {"frame_index": idx.astype(np.float64), "records": r.astype(np.float32),
+              "ext": e.astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"frames": int(idx.size), "of": int(records.shape[0]),
+            "arrays": {k: list(a.shape) for k, a in arrays.items()}}
+
+
 def config5_leg(zp, total, steps, warmup, world, rank, dev, barrier, coll_dev):
     """BASELINE config 5 in the same ranks: the `total`-frame IMIX stream cut
     into `world` contiguous shards, rank r parsing frames [total*r/world,
@@ -339,6 +391,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--packets", type=int, default=0, help="frames per GPU (default: config)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the placement probes, the PCIe-inclusive leg, the CPU "
+                         "baseline and the config-5 leg (--no-pcie / --no-cpu / --no-c5 take "
+                         "single legs out again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's records / ext (a seeded sample of "
+                         f"{DUMP_FRAMES} frames) as DIR/<name>.npy")
     ap.add_argument("--cpu-sample", type=int, default=1 << 20)
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--no-cpu", action="store_true")
@@ -461,8 +520,12 @@ def main():
                      "algorithmic_bytes_per_launch": total_bytes},
     }
     coll_dev = "cpu" if shared else dev
-    out["roofline"]["placement"] = placement_probe(zp, arena, offs, lens, records, kmean)
-    if not args.no_pcie:
+    if args.dump_outputs and rank == 0:
+        # before any --full leg: the probes store into `records`
+        out["dumped"] = dump_outputs(zp, args.dump_outputs, records, ext)
+    if args.full:
+        out["roofline"]["placement"] = placement_probe(zp, arena, offs, lens, records, kmean)
+    if args.full and not args.no_pcie:
         # every rank's host path at once: frames of all ranks / the slowest rank
         m, nb, sec, perr = pcie_inclusive(zp, arena, offs, lens, 1 << 21, barrier)
         rows = gather_rows([m, nb, sec, perr], world, rank, coll_dev)
@@ -474,14 +537,14 @@ def main():
             "per_rank_gb_per_s": [round(float(b) / s / 1e9, 2) for b, s in rows[:, 1:3]],
             "rejected_frames": int(rows[:, 3].sum()),
             "path": PCIE_PATH + ("; all ranks concurrently, summed" if world > 1 else "")}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(zp, arena, offs, lens, args.cpu_sample,
                                            args.cpu_seconds)
         # vs_baseline stays null: BASELINE.md has no published number for
         # this metric. The ratio to the CPU leg of this run is reported
         # beside it instead.
         out["vs_cpu_baseline"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
-    if args.config != "c5" and not args.no_c5:
+    if args.full and args.config != "c5" and not args.no_c5:
         # BASELINE config 5 (256M-frame IMIX over the N GPUs, strong scaling)
         # in the same ranks, so every 1/2/4/8-GPU line carries it
         del arena, offs, lens, records, ext

@@ -27,6 +27,21 @@ def test_host_cores_reports_affinity():
         assert threads <= max(1, int(quota))
 
 
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: every frame of a small batch, else the same sorted
+    DUMP_FRAMES distinct indices on every call; 160 B per frame as float32
+    records + ext and 8 B of index stay under 64 MB."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert np.array_equal(bench.dump_sample(1000), np.arange(1000))
+    assert np.array_equal(bench.dump_sample(bench.DUMP_FRAMES), np.arange(bench.DUMP_FRAMES))
+    a, b = bench.dump_sample(1 << 24), bench.dump_sample(1 << 24)
+    assert np.array_equal(a, b) and a.dtype == np.int64 and a.shape == (bench.DUMP_FRAMES,)
+    assert (np.diff(a) > 0).all() and a[0] >= 0 and a[-1] < 1 << 24
+    assert bench.DUMP_FRAMES * (4 * (8 + 2 * 16) + 8) <= 64 * 10**6
+
+
 def test_parse_count_suffixes():
     sys.path.insert(0, ROOT)
     import bench

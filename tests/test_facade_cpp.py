@@ -162,12 +162,16 @@ def _compile_snippet(body, tmp_path):
 
 @pytest.mark.parametrize("body,ok", [
     (".ethernet(m, m, 2048).ipv4(4, 5, 0, 0, 50, 0, 0, 0, 64, 17, a, a).udp(a, 1, a, 2, 30)", True),
-    (".ethernet(m, m, 34525).ipv6(6, 0, 0, 0, 0, 64, a6, a6).hop_by_hop(0, 1, zp::Bytes{})"
-     ".routing_header(0, 1, 0, 0, zp::Bytes{}).ipv4(4, 5, 0, 0, 0, 0, 0, 0, 1, 6, a, a)"
-     ".tcp(a, 1, a, 2, 3, 4, 5, 0, 2, 9, 0)", True),
+    # explicit ids where the snippet holds "::", the separator of a test id
+    pytest.param(
+        ".ethernet(m, m, 34525).ipv6(6, 0, 0, 0, 0, 64, a6, a6).hop_by_hop(0, 1, zp::Bytes{})"
+        ".routing_header(0, 1, 0, 0, zp::Bytes{}).ipv4(4, 5, 0, 0, 0, 0, 0, 0, 1, 6, a, a)"
+        ".tcp(a, 1, a, 2, 3, 4, 5, 0, 2, 9, 0)", True, id="ipv6_hbh_routing_ipv4_tcp-True"),
     (".ethernet(m, m, 2048).tcp(a, 1, a, 2, 3, 4, 5, 0, 2, 9, 0)", False),          # no L3
-    (".ethernet(m, m, 34525).ipv6(6, 0, 0, 0, 0, 64, a6, a6)"
-     ".destination_options1(0, 1, zp::Bytes{}).fragment_header(0, 0, false, 0)", False),
+    pytest.param(
+        ".ethernet(m, m, 34525).ipv6(6, 0, 0, 0, 0, 64, a6, a6)"
+        ".destination_options1(0, 1, zp::Bytes{}).fragment_header(0, 0, false, 0)", False,
+        id="ipv6_dstopts1_then_fragment-False"),
     (".ethernet(m, m, 2048).ipv4(4, 5, 0, 0, 0, 0, 0, 0, 1, 58, a, a).icmpv6(a6, a6, 1, 0)", False),
     (".ethernet(m, m, 2048).ipv4(4, 5, 0, 0, 0, 0, 0, 0, 1, 6, a, a).tcp(a6, 1, a6, 2, 3, 4, 5, 0, 2, 9, 0)",
      False),                                                                         # &[u8; 4] state

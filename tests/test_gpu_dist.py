@@ -25,8 +25,8 @@ def test_bench_two_ranks():
     n = 1 << 20
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--config", "c3", "--packets", str(n), "--no-c5"]
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3",
+           "--warmup", "1", "--config", "c3", "--packets", str(n), "--no-c5"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -45,7 +45,7 @@ def test_bench_spawns_ranks_itself():
     """`python bench.py --gpus 2` with no launcher around it (the driver's
     command) starts both ranks itself and reports n_gpus == 2."""
     n = 1 << 20
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3",
            "--warmup", "1", "--packets", str(n), "--c5-frames", "2M"]
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
@@ -63,11 +63,11 @@ def test_bench_spawns_ranks_itself():
 def test_bench_config5_and_host_path_over_ranks():
     """The driver's multi-GPU command also measures BASELINE config 5 (the IMIX
     stream split over the ranks, strong scaling) and the PCIe-inclusive rate
-    of every rank at once: plain `python bench.py --gpus 2
+    of every rank at once: `python bench.py --full --gpus 2
     --c5-frames 8M`, no launcher around it."""
     total = 8 << 20
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--packets", str(1 << 20), "--c5-frames", "8M"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2",
+           "--steps", "3", "--warmup", "1", "--packets", str(1 << 20), "--c5-frames", "8M"]
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
@@ -93,12 +93,12 @@ def test_bench_rccl_path_one_rank():
     """The RCCL branch of the multi-GPU line (init_process_group("nccl",
     device_id=...), barrier(device_ids=...), the all-reduces of the timing
     and of the per-rank rows) on one GPU: `torch.distributed.run
-    --nproc-per-node 1 bench.py --gpus 1 --dist` (a one-GPU box cannot start
+    --nproc-per-node 1 bench.py --full --gpus 1 --dist` (a one-GPU box cannot start
     two RCCL ranks; the 8-GPU node runs the same code with one rank per GPU)."""
     n = 1 << 20
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}",
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist", "--steps", "3",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--dist", "--steps", "3",
            "--warmup", "1", "--config", "c3", "--packets", str(n), "--c5-frames", "2M",
            "--no-cpu"]
     env = dict(os.environ, OMP_NUM_THREADS="1")

@@ -23,8 +23,8 @@ for s in "$@"; do
     build)  step build 600 python __graft_entry__.py ;;
     tests)  step gpu_tests 1200 python -u -m pytest tests -m gpu -q -p no:cacheprovider --timeout 300 --timeout-method thread ;;
     smoke)  step smoke 300 python __graft_entry__.py smoke ;;
-    bench)  step bench 900 python bench.py ;;
-    prof)   step prof 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --no-pcie ;;
+    bench)  step bench 900 python bench.py --full ;;
+    prof)   step prof 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --full --no-pcie ;;
     *) step "step$i" 900 bash -c "$s" ;;
   esac
 done
