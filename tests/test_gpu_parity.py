@@ -189,9 +189,11 @@ def test_min_size_tiles_repaired(zp):
     assert {9, 12, 26, 29} <= set(np.unique(want["err"]).tolist())
 
 
-@pytest.mark.parametrize("layout", ["shuffled", "gaps", "overlap", "reverse", "dup"])
-def test_layouts(zp, golden, layout):
-    frames = fuzz_frames(zp, golden, 5000, 11)
+LAYOUTS = ["shuffled", "gaps", "overlap", "reverse", "dup"]
+
+
+def layout_batch(frames, layout):
+    """frames -> (arena, offs, lens) with the descriptors in one of LAYOUTS."""
     arena, offs, lens = pack(frames, base_pad=3, gap=(13 if layout == "gaps" else 0))
     rng = np.random.default_rng(3)
     if layout == "shuffled":
@@ -206,6 +208,13 @@ def test_layouts(zp, golden, layout):
     elif layout == "dup":
         idx = rng.integers(0, len(offs), 8000)
         offs, lens = offs[idx], lens[idx]
+    return arena, offs, lens
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_layouts(zp, golden, layout):
+    frames = fuzz_frames(zp, golden, 5000, 11)
+    arena, offs, lens = layout_batch(frames, layout)
     got, gext = gpu_parse(zp, arena, offs, lens)
     want, wext = orc.parse_batch(arena, offs, lens)
     assert_same(got, gext, want, wext)
@@ -287,14 +296,27 @@ def _jumbo_ipv6(total_len, rng, valid=True, proto=17, fill=None):
     return bytes(f)
 
 
-def test_jumbo_frames_exact_path(zp):
-    """Segments > 64 KiB take the exact E/O path (u32 wrap reproduced)."""
+def jumbo_frames():
+    """65,535-300,000 B, UDP and ICMPv6, valid and corrupt checksums."""
     rng = np.random.default_rng(5)
     frames = []
     for L in (65535, 65600, 70001, 140000, 200003, 300000):
         for proto in (17, 58):
             frames.append(_jumbo_ipv6(L, rng, True, proto))
             frames.append(_jumbo_ipv6(L, rng, False, proto))
+    return frames
+
+
+def word_sum_frames():
+    """65,534-65,537 B of 0xFF, valid and corrupt ICMPv6 checksums in turn."""
+    rng = np.random.default_rng(9)
+    return [_jumbo_ipv6(L, rng, ok, 58, fill=0xFF)
+            for L in (65534, 65535, 65536, 65537) for ok in (True, False)]
+
+
+def test_jumbo_frames_exact_path(zp):
+    """Segments > 64 KiB take the exact E/O path (u32 wrap reproduced)."""
+    frames = jumbo_frames()
     arena, offs, lens = pack(frames)
     got, gext = gpu_parse(zp, arena, offs, lens, base_shift=1)
     want, wext = orc.parse_batch(arena, offs, lens)
@@ -308,9 +330,7 @@ def test_word_sum_bounds(zp):
     exact path (65,537 B), all-0xFF payloads (the largest word sums the u32
     stream arithmetic meets), valid and corrupt ICMPv6 checksums, at both
     arena parities."""
-    rng = np.random.default_rng(9)
-    frames = [_jumbo_ipv6(L, rng, ok, 58, fill=0xFF)
-              for L in (65534, 65535, 65536, 65537) for ok in (True, False)]
+    frames = word_sum_frames()
     arena, offs, lens = pack(frames)
     want, wext = orc.parse_batch(arena, offs, lens)
     assert list(want["err"][0::2]) == [0, 0, 0, 0]
