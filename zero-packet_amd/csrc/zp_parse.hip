@@ -49,8 +49,6 @@
 #define ZP_WAVES 1           // waves per workgroup (independent waves; 1 = finest LDS granularity)
 #define ZP_EXT_DENSE 32      // chains per wave from which all 64 ext entries are written
 #define ZP_K 1               // consecutive tiles per wave
-#define ZP_SMALL_G 4         // tiles of at most this many stream items take one small group (0: off)
-#define ZP_TAIL_G 4          // a tile's last <= this many items as one small group (0: off)
 // Rejected variants, timing ablations and diagnostic stamps live in
 // tools/patches/lab.patch, applied to a scratch copy by
 // tools/build_variants.sh (tools/kbench.py --variants); this file is the
@@ -987,53 +985,23 @@ __device__ __forceinline__ void parse_tile(uint64_t t, uint32_t len, uintptr_t g
                                            zp_record* __restrict__ records,
                                            zp_ext_offsets* __restrict__ ext,
                                            const ColPtrs& cols) {
-    const uintptr_t fallback = (uintptr_t)&zp_safe_chunk;   // dummy loads when T == 0
     uint4* win = &lds.win[0];
     uint4* tail = &lds.win[0] + ZP_WIN_CH * 64;
     // a tile of 64-B frames: registers only (wave-uniform test)
     if (TINY && !__ballot(t * 64 + lane < n && len != 64u) &&
         tiny_tile(t, len, ga, n, lane, records, SLOTS))
         return;
+    // The tile number again, as scalars the compiler cannot match: it would
+    // otherwise share the record addresses with the register path above,
+    // compute them here and carry them through the stream (2 VGPRs, spilled
+    // in the slots kernel).
+    t = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(t >> 32)) << 32) |
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)t);   // (wave-uniform anyway)
     TileState s;
     tile_setup(s, t, len, ga, n, lane, lds);
-    // stream: one group of ZP_G items per iteration (group 0 outside the
-    // loop, so no load is in flight across the loop back-edge)
-    if (s.nitems <= ZP_SMALL_G) {              // wave-uniform: a tile of small frames
-        // One group of ZP_SMALL_G items holds the whole tile (c2: 4 KiB):
-        // no dummy loads past the tile's end (c2 -8 %, c5 -1 %, c3/c4 0).
-        uint4 vs[ZP_SMALL_G];
-        uint32_t ks[ZP_SMALL_G];
-        issue_group<ZP_SMALL_G>(0, s.nitems, s.cur, s.R, lane, fallback, vs, ks);
-        consume_group<ZP_SMALL_G>(0, s.nitems, lane, vs, ks, win, tail, lds.cend, s.run);
-    } else
-    {
-    uint4 va[ZP_G];
-    uint32_t ka[ZP_G];
-    issue_group<ZP_G>(0, s.nitems, s.cur, s.R, lane, fallback, va, ka);
-    consume_group<ZP_G>(0, s.nitems, lane, va, ka, win, tail, lds.cend, s.run);
-    for (uint32_t i0 = ZP_G; i0 < s.nitems; i0 += ZP_G) {
-        if (s.nitems - i0 <= 2) {                 // the last 1-2 items as a pair
-            uint4 vt[2];
-            uint32_t kt[2];
-            issue_group<2>(i0, s.nitems, s.cur, s.R, lane, fallback, vt, kt);
-            consume_group<2>(i0, s.nitems, lane, vt, kt, win, tail, lds.cend, s.run);
-            break;
-        }
-        // The last <= ZP_TAIL_G items as a small group: fewer dummy loads
-        // past the tile's end, whose address work (4 ds_bpermute each) and
-        // consume are not free (c5 -1.7 %, c6 -1.1 %, c3 -0.3 %, c4 0;
-        // profiles/r04_kbench_tail_group.log). Wave-uniform.
-        if (s.nitems - i0 <= ZP_TAIL_G) {
-            uint4 vt[ZP_TAIL_G];
-            uint32_t kt[ZP_TAIL_G];
-            issue_group<ZP_TAIL_G>(i0, s.nitems, s.cur, s.R, lane, fallback, vt, kt);
-            consume_group<ZP_TAIL_G>(i0, s.nitems, lane, vt, kt, win, tail, lds.cend, s.run);
-            break;
-        }
-        issue_group<ZP_G>(i0, s.nitems, s.cur, s.R, lane, fallback, va, ka);
-        consume_group<ZP_G>(i0, s.nitems, lane, va, ka, win, tail, lds.cend, s.run);
-    }
-    }
+    // stream: a rolling window of ZP_G loads, exactly the tile's items
+    // (zp_stream.h; a tile none of whose frames owns a chunk loads nothing)
+    stream_window(s.nitems, s.cur, s.R, lane, win, tail, lds.cend, s.run);
     wave_lds_fence();                          // LDS written by other lanes
     // The frame address again, from its rank's stream origin (live
     // through the stream anyway) instead of keeping it there: two VGPRs

@@ -328,6 +328,183 @@ __device__ __forceinline__ void consume_group(uint32_t i0, uint32_t nitems, int 
 }
 
 // --------------------------------------------------------------------------
+// The parse kernels' stream: a rolling window of ZP_G loads (the builder keeps
+// the groups above). After a prologue that issues ZP_G items, each step waits
+// for the oldest load, consumes its item and at once issues item + ZP_G into
+// the registers just freed, so 7-8 loads stay in flight from the first item
+// to the last instead of draining to zero after every group. Exactly the
+// tile's items are loaded: the items left after the last full round
+// (wave-uniform) pick one of ZP_G straight-line epilogues, and a tile of fewer
+// than ZP_G items one right-sized group.
+//
+// The loads are ordinary compiler-visible nontemporal loads, in flight across
+// the loop back-edge: every slot is a loop-carried value and the same number
+// of loads is outstanding on every edge into a block, so LLVM's wait insertion
+// comes to s_waitcnt vmcnt(7) at every wait of the loop, 7 .. 0 in the
+// epilogues and N - 1 .. 0 in a short tile (checked in the gfx950 assembly,
+// DESIGN §3.2). Inline-asm loads and waits were built first and are wrong: the
+// register allocator copied a slot's registers ahead of the asm wait, while
+// the load was still in flight. The stream has no other vector memory
+// operation between its first issue and its last wait.
+// --------------------------------------------------------------------------
+__device__ __forceinline__ void win_load(zp_u32x4& v, uintptr_t a) {
+    v = __builtin_nontemporal_load((const ZP_GLOBAL zp_u32x4*)a);
+    asm volatile("" ::: "memory");
+}
+// Places the wait for v: an empty asm that reads it, so the compiler waits
+// here and not at the first use it schedules. N, for the reader and the ISA
+// check: the loads younger than v still in flight, i.e. the vmcnt(N) expected.
+template <int N>
+__device__ __forceinline__ void win_wait(zp_u32x4& v) {
+    static_assert(N >= 0 && N < ZP_G, "window depth");
+    asm volatile("" ::"v"(v) : "memory");
+}
+
+// The start masks of the ZP_STARTS items around item i, one per lane
+// (lane l: item (i & ~(ZP_STARTS - 1)) + l), rebuilt and read when i is the
+// first of them: one LDS read per ZP_STARTS items, a v_readlane pair per item.
+struct StartRegs { uint32_t lo, hi; };
+__device__ __forceinline__ void win_masks(uint32_t i, StartRegs& m, const Cursor& c,
+                                          const Ranked& R, int lane) {
+    static_assert(ZP_STARTS <= 64 && ZP_STARTS % ZP_G == 0, "one start mask per lane");
+    if ((i & (ZP_STARTS - 1u)) != 0) return;                  // wave-uniform
+    build_starts(i, c, R, lane);
+    const zp_u32x2 w = *(const zp_u32x2*)&c.starts[lane & (ZP_STARTS - 1)];
+    m.lo = w.x;
+    m.hi = w.y;
+}
+
+// Issues item i (< nitems) into one slot.
+__device__ __forceinline__ void win_issue(uint32_t i, Cursor& c, const Ranked& R,
+                                          const StartRegs& m, int lane, zp_u32x4& v,
+                                          uint32_t& keep) {
+    const uint32_t sl = i & (ZP_STARTS - 1u);
+    const uint32_t flo = rdl(m.lo, sl), fhi = rdl(m.hi, sl);
+    const uint64_t F = ((uint64_t)fhi << 32) | flo;
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi(fhi, __builtin_amdgcn_mbcnt_lo(flo, 0u));
+    uint32_t r = c.rbase + below + (uint32_t)((F >> lane) & 1u);
+    r = r < c.nz ? r : c.nz - 1u;           // past the last frame (and never a stray lane)
+    c.rbase += (uint32_t)__builtin_popcountll(F);
+    const uint32_t vv = 64u * i + (uint32_t)lane;
+    const uint32_t olo = bperm(R.org_lo, r), ohi = bperm(R.org_hi, r);
+    const uint32_t lv = bperm(R.last, r), fp = bperm(R.pfx, r);
+    const uint32_t ci = vv - fp;                              // chunk index within the frame
+    uint32_t k = (r & 63u) << 16;
+    k |= ci < ZP_WIN_CH ? KEEP_WIN | (ci * 64u + ((r ^ ci) & 63u)) : 0u;
+    k |= vv == lv ? KEEP_TAIL : 0u;
+    keep = vv <= lv ? k | KEEP_IN : 0u;
+    // The descriptor is final here: left alone, the scheduler carries r, lv,
+    // fp and vv of every slot to the end of the round instead (4 VGPRs a slot
+    // for 1, and the kernel spills).
+    asm volatile("" : "+v"(keep));
+    const uint32_t vc = vv < lv ? vv : lv;  // lanes past the tile's end re-read its last chunk
+    win_load(v, (((uintptr_t)ohi << 32) | olo) + 16ull * vc);
+}
+
+// Consumes one landed item (consume_group's body for one slot).
+__device__ __forceinline__ void win_consume(const zp_u32x4& v, uint32_t k, uint4* win, uint4* tail,
+                                            uint32_t* cend, uint32_t& run) {
+    const uint4 d = make_uint4(v.x, v.y, v.z, v.w);
+    if (k & KEEP_WIN) win[KEEP_CELL(k)] = d;
+    uint32_t part = sad16(d.x, 0u);
+    part = sad16(d.y, part);
+    part = sad16(d.z, part);
+    part = sad16(d.w, part);
+    const uint32_t P = wave_scan(k & KEEP_IN ? part : 0u);
+    if (k & KEEP_TAIL) {
+        if (tail != nullptr) tail[KEEP_RANK(k)] = d;
+        cend[KEEP_RANK(k)] = run + P;
+    }
+    run += rdl(P, 63);
+}
+
+// A whole tile of N < ZP_G items.
+template <int N>
+__device__ __forceinline__ void win_small(Cursor& c, const Ranked& R, const StartRegs& m, int lane,
+                                          uint4* win, uint4* tail, uint32_t* cend, uint32_t& run) {
+    zp_u32x4 v[N];
+    uint32_t k[N];
+#pragma unroll
+    for (int q = 0; q < N; ++q) win_issue((uint32_t)q, c, R, m, lane, v[q], k[q]);
+#define ZP_WIN_STEP(q) \
+    if constexpr (q < N) { win_wait<N - 1 - q>(v[q]); \
+                           win_consume(v[q], k[q], win, tail, cend, run); }
+    ZP_WIN_STEP(0) ZP_WIN_STEP(1) ZP_WIN_STEP(2) ZP_WIN_STEP(3)
+    ZP_WIN_STEP(4) ZP_WIN_STEP(5) ZP_WIN_STEP(6)
+#undef ZP_WIN_STEP
+}
+
+// The end of a longer tile: items i0 .. i0 + 7 are in flight in slots 0-7 and
+// REM more remain. REM steps that still issue, then the drain: 7 .. 0 loads
+// outstanding at its waits.
+template <int REM>
+__device__ __forceinline__ void win_tail(uint32_t i0, Cursor& c, const Ranked& R, StartRegs& m,
+                                         int lane, zp_u32x4 (&v)[ZP_G], uint32_t (&k)[ZP_G],
+                                         uint4* win, uint4* tail, uint32_t* cend, uint32_t& run) {
+    if (REM) win_masks(i0 + ZP_G, m, c, R, lane);
+#define ZP_WIN_STEP(q) \
+    if constexpr (q < REM) { win_wait<ZP_G - 1>(v[q]); \
+                             win_consume(v[q], k[q], win, tail, cend, run); \
+                             win_issue(i0 + ZP_G + q, c, R, m, lane, v[q], k[q]); }
+    ZP_WIN_STEP(0) ZP_WIN_STEP(1) ZP_WIN_STEP(2) ZP_WIN_STEP(3)
+    ZP_WIN_STEP(4) ZP_WIN_STEP(5) ZP_WIN_STEP(6)
+#undef ZP_WIN_STEP
+    // slots REM .. 7 (the older round), then 0 .. REM - 1
+#define ZP_WIN_STEP(d) { \
+        constexpr int q = (REM + d) % ZP_G; \
+        win_wait<ZP_G - 1 - d>(v[q]); \
+        win_consume(v[q], k[q], win, tail, cend, run); }
+    ZP_WIN_STEP(0) ZP_WIN_STEP(1) ZP_WIN_STEP(2) ZP_WIN_STEP(3)
+    ZP_WIN_STEP(4) ZP_WIN_STEP(5) ZP_WIN_STEP(6) ZP_WIN_STEP(7)
+#undef ZP_WIN_STEP
+}
+
+__device__ __forceinline__ void stream_window(uint32_t nitems, Cursor& c, const Ranked& R, int lane,
+                                              uint4* win, uint4* tail, uint32_t* cend,
+                                              uint32_t& run) {
+    static_assert(ZP_G == 8, "the window's slots and epilogues are written out for 8");
+    if (nitems == 0) return;                                  // no frame owns a chunk: no load
+    StartRegs m{0u, 0u};
+    win_masks(0, m, c, R, lane);
+    if (nitems < ZP_G) {                                      // wave-uniform
+        switch (nitems) {
+        case 1: win_small<1>(c, R, m, lane, win, tail, cend, run); break;
+        case 2: win_small<2>(c, R, m, lane, win, tail, cend, run); break;
+        case 3: win_small<3>(c, R, m, lane, win, tail, cend, run); break;
+        case 4: win_small<4>(c, R, m, lane, win, tail, cend, run); break;
+        case 5: win_small<5>(c, R, m, lane, win, tail, cend, run); break;
+        case 6: win_small<6>(c, R, m, lane, win, tail, cend, run); break;
+        default: win_small<7>(c, R, m, lane, win, tail, cend, run); break;
+        }
+        return;
+    }
+    zp_u32x4 v[ZP_G];
+    uint32_t k[ZP_G];
+#pragma unroll
+    for (int q = 0; q < ZP_G; ++q) win_issue((uint32_t)q, c, R, m, lane, v[q], k[q]);
+    uint32_t i0 = 0;
+    for (; i0 + 2 * ZP_G <= nitems; i0 += ZP_G) {             // a full round: 8 steps
+        win_masks(i0 + ZP_G, m, c, R, lane);
+#pragma unroll
+        for (int q = 0; q < ZP_G; ++q) {
+            win_wait<ZP_G - 1>(v[q]);
+            win_consume(v[q], k[q], win, tail, cend, run);
+            win_issue(i0 + ZP_G + q, c, R, m, lane, v[q], k[q]);
+        }
+    }
+    switch (nitems - i0 - ZP_G) {                             // wave-uniform, 0 .. 7
+    case 0: win_tail<0>(i0, c, R, m, lane, v, k, win, tail, cend, run); break;
+    case 1: win_tail<1>(i0, c, R, m, lane, v, k, win, tail, cend, run); break;
+    case 2: win_tail<2>(i0, c, R, m, lane, v, k, win, tail, cend, run); break;
+    case 3: win_tail<3>(i0, c, R, m, lane, v, k, win, tail, cend, run); break;
+    case 4: win_tail<4>(i0, c, R, m, lane, v, k, win, tail, cend, run); break;
+    case 5: win_tail<5>(i0, c, R, m, lane, v, k, win, tail, cend, run); break;
+    case 6: win_tail<6>(i0, c, R, m, lane, v, k, win, tail, cend, run); break;
+    default: win_tail<7>(i0, c, R, m, lane, v, k, win, tail, cend, run); break;
+    }
+}
+
+// --------------------------------------------------------------------------
 // The batch kernel.
 // --------------------------------------------------------------------------
 // One tile = 64 consecutive frames on one wave (lane = frame).
