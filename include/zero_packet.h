@@ -577,6 +577,60 @@ int zp_parse_batch_columns_device(const uint8_t* arena, const uint64_t* offs,
                                   zp_ext_offsets* ext, void* const* cols, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Batched header rewrite: the writers' field setters over frames that exist  */
+/* already (EthernetWriter::set_src_mac, IPv4Writer::set_ttl / set_src_ip,    */
+/* IPv6Writer::set_hop_limit, TcpWriter::set_src_port ...), with the          */
+/* checksums refreshed. The inverse of the column views: extract, edit the    */
+/* columns, write them back (NAT, TTL decrement, DSCP re-marking, VLAN        */
+/* re-tagging, MAC rewrite) without a host pass and without touching the      */
+/* payload.                                                                   */
+/*                                                                            */
+/* Writable columns: DEST_MAC, SRC_MAC (the MAC bytes), VLAN_TCI,             */
+/* VLAN_INNER_TCI (the TCI only; the TPIDs stay), SRC_ADDR, DEST_ADDR (outer  */
+/* IP), TTL (ttl / hop limit), TOS (IPv4 byte 1 whole / IPv6 traffic class),  */
+/* IP_ID (IPv4 id from the low 16 bits / IPv6 flow label from the low 20),    */
+/* SRC_PORT, DEST_PORT (TCP or UDP), TCP_SEQ, TCP_ACK, TCP_WINDOW.            */
+/*                                                                            */
+/* 1. A frame whose record holds an error or no Ethernet reader is left       */
+/*    byte for byte as it is.                                                 */
+/* 2. Entry i of a column applies to frame i exactly when the extract of that */
+/*    column would read a present reader (TCP_* with a TCP reader, ports with */
+/*    TCP or UDP, the IP columns with an outer IPv4 / IPv6 reader, VLAN_TCI   */
+/*    with one or two tags, VLAN_INNER_TCI with two); other entries are       */
+/*    ignored.                                                                */
+/* 3. Afterwards the frame is what the writers give: the setters of the       */
+/*    applied fields, then IPv4Writer::set_checksum (ipv4.rs:119-126) under   */
+/*    an outer IPv4, then the L4 writer's set_checksum(pseudo_sum) over the   */
+/*    L4 slice to the frame end (tcp.rs:123-129, udp.rs:65-71,                */
+/*    icmpv4.rs:74-80, icmpv6.rs:71-77). A checksum none of whose covered     */
+/*    words (pseudo-header included) got another value is not written, so     */
+/*    rewrite(extract(x)) is the identity even over a valid checksum stored   */
+/*    as 0xFFFF where a recompute stores 0x0000.                              */
+/* 4. The L4 checksum covers the outer addresses as parser.rs:311-362 has it: */
+/*    only without ip_in_ip, and not for ICMPv4 under an outer IPv4.          */
+/* 5. Nothing else changes: lengths, offsets and presence stay, so the        */
+/*    batch's records hold for the rewritten frames.                          */
+/* The checksums are updated from the changed words (RFC 1624), which equals  */
+/* the recompute because the parse verified them: the frames must be          */
+/* unchanged since that parse.                                                */
+/* ------------------------------------------------------------------------- */
+
+/* 1 if column `col` can be written back by zp_rewrite_columns_device, else 0. */
+int zp_col_writable(int col);
+
+/* The writers' setters over n parsed frames, in place. cols is indexed by
+ * zp_col exactly as for zp_extract_columns_device (same element widths, same
+ * byte order, same 16-B address layout with IPv4 in bytes 0-3); NULL = leave
+ * that field alone. arena/offs/lens/records are the batch and the records the
+ * parse wrote for it; the frames must not have changed since that parse and
+ * must not overlap. Device memory; enqueues on `stream`. A non-NULL pointer
+ * for a column that is not writable returns a negative value before anything
+ * is launched (zp_last_error names the column). */
+int zp_rewrite_columns_device(uint8_t* arena, const uint64_t* offs,
+                              const uint32_t* lens, const zp_record* records,
+                              uint64_t n, const void* const* cols, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Batched PacketBuilder. The reference builds one    */
 /* frame with a typestate chain over a caller-sized buffer                    */
 /* (builder.rs:55-909): PacketBuilder::new(&mut buf).ethernet(..).ipv4(..)    */

@@ -594,6 +594,14 @@ inline void parse_batch_device(const uint8_t* arena, const uint64_t* offs, const
         throw std::runtime_error(std::string("zp_parse_batch_device: ") + zp_last_error());
 }
 
+// Columns written back into parsed frames, checksums refreshed
+// (zp_rewrite_columns_device): cols[ZP_COL_COUNT], nullptr = leave alone.
+inline void rewrite_columns(uint8_t* arena, const uint64_t* offs, const uint32_t* lens,
+                            const zp_record* records, uint64_t n, const void* const* cols,
+                            void* stream) {
+    if (zp_rewrite_columns_device(arena, offs, lens, records, n, cols, stream) < 0)
+        throw std::runtime_error(std::string("zp_rewrite_columns_device: ") + zp_last_error());
+}
 
 // Per-batch counters (zp_stats_device): adds into counts[ZP_STATS_COUNT].
 inline void stats_device(const zp_record* records, uint64_t n, uint64_t* counts, void* stream) {
