@@ -612,8 +612,32 @@ int zp_parse_batch_columns_device(const uint8_t* arena, const uint64_t* offs,
 /*    batch's records hold for the rewritten frames.                          */
 /* The checksums are updated from the changed words (RFC 1624), which equals  */
 /* the recompute because the parse verified them: the frames must be          */
-/* unchanged since that parse.                                                */
+/* unchanged since that parse. The payload is not read, with one exception:   */
+/* the reference sums into a u32 that wraps (checksum.rs:5-29), and a sum     */
+/* that can reach 2^32 is no longer a sum mod 65535. For a frame whose L4     */
+/* slice has ZP_REWRITE_EXACT_L4_BYTES or more (IPv6 jumbograms with TCP or   */
+/* ICMP) and whose L4 checksum changes, the new L4 slice is summed in full    */
+/* with that wrap, as the L4 writers do.                                      */
 /* ------------------------------------------------------------------------- */
+
+/* The shortest L4 slice (frame length - L4 offset) whose word sum plus        */
+/* pseudo-header can reach 2^32: below it, with L the slice's length,          */
+/* ceil(L / 2) * 0xFFFF (its words, the checksum field included)               */
+/* + 16 * 0xFFFF (two IPv6 addresses) + 255 (protocol) + L (length) < 2^32,    */
+/* so the reference's sum never wraps and the update from the changed words   */
+/* is exact. The bound grows with L; it holds at 131,036 and fails at 131,037. */
+#define ZP_REWRITE_EXACT_L4_BYTES 131037u
+#define ZP_REWRITE_SUM_BOUND(L) \
+    (((L) + 1ull) / 2 * 0xFFFFull + 16 * 0xFFFFull + 255ull + (L))
+#if defined(__cplusplus)
+static_assert(ZP_REWRITE_SUM_BOUND(ZP_REWRITE_EXACT_L4_BYTES - 1ull) < (1ull << 32) &&
+              ZP_REWRITE_SUM_BOUND(ZP_REWRITE_EXACT_L4_BYTES + 0ull) >= (1ull << 32),
+              "ZP_REWRITE_EXACT_L4_BYTES is the first length at which the L4 sum can wrap");
+#else
+_Static_assert(ZP_REWRITE_SUM_BOUND(ZP_REWRITE_EXACT_L4_BYTES - 1ull) < (1ull << 32) &&
+               ZP_REWRITE_SUM_BOUND(ZP_REWRITE_EXACT_L4_BYTES + 0ull) >= (1ull << 32),
+               "ZP_REWRITE_EXACT_L4_BYTES is the first length at which the L4 sum can wrap");
+#endif
 
 /* 1 if column `col` can be written back by zp_rewrite_columns_device, else 0. */
 int zp_col_writable(int col);

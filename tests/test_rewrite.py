@@ -176,15 +176,40 @@ def random_cols(rng, n, names):
     return cols
 
 
-def run_rewrite(zp, arena, offs, lens, cols, base=0, stream=None):
+GUARD = 0xA5
+
+
+def as_extracted(name, wr, orec):
+    """A written column as the extract reads it back where it applied."""
+    if name in ("src_addr", "dest_addr"):               # IPv4: bytes 0-3, the rest reads 0
+        wr = wr.copy()
+        wr[(orec["flags"] & 4) != 0, 4:] = 0
+    elif name == "ip_id":                               # 16 bits of IPv4 id, 20 of flow label
+        wr = np.where((orec["flags"] & 4) != 0, wr & 0xFFFF, wr & 0xFFFFF).astype(wr.dtype)
+    return wr
+
+
+def frames_at(offs, lens, where):
+    """The descriptor index that owns each arena offset in `where` (-1: none,
+    a byte between or outside the frames), for descriptors in any order."""
+    offs, lens = np.asarray(offs).astype(np.int64), np.asarray(lens).astype(np.int64)
+    order = np.argsort(offs, kind="stable")
+    j = np.searchsorted(offs[order], where, side="right") - 1
+    own = order[np.maximum(j, 0)]
+    return np.where((j >= 0) & (np.asarray(where) < offs[own] + lens[own]), own, -1)
+
+
+def run_rewrite(zp, arena, offs, lens, cols, base=0, stream=None, guard=64):
     """Parses and rewrites on the GPU; checks (a) bytes == rewrite_ref, (b) the
     oracle re-parses the output to the same packed records, (c) the oracle's
     columns of the output. Returns (output arena, changed masks, oracle records).
-    base: leading bytes in front of the arena view (shifts its alignment)."""
+    base: leading bytes in front of the arena view (shifts its alignment);
+    guard: bytes behind it (0: the arena ends on the allocation's last byte).
+    Both hold GUARD before and must hold it afterwards."""
     import torch
     d = torch.device("cuda:0")
-    whole = torch.zeros(base + len(arena), dtype=torch.uint8, device=d)
-    a = whole[base:]
+    whole = torch.full((base + len(arena) + guard,), GUARD, dtype=torch.uint8, device=d)
+    a = whole[base:base + len(arena)]
     a.copy_(torch.from_numpy(arena))
     o = torch.from_numpy(offs.astype(np.int64)).to(d)
     l_ = torch.from_numpy(lens.astype(np.int32)).to(d)
@@ -205,8 +230,8 @@ def run_rewrite(zp, arena, offs, lens, cols, base=0, stream=None):
     want, changed, applied = rewrite_batch_ref(arena, offs, lens, orec, oext, cols)
     bad = np.nonzero(got != want)[0]
     assert bad.size == 0, ("bytes differ from rewrite_ref at arena offsets", bad[:8],
-                           "frames", np.searchsorted(offs, bad[:8], side="right") - 1)   # (a)
-    assert not whole[:base].any()
+                           "frames", frames_at(offs, lens, bad[:8]))                      # (a)
+    assert (whole[:base] == GUARD).all() and (whole[base + len(arena):] == GUARD).all()
     nrec, next_ = orc.parse_batch(got, offs, lens)
     assert orc.pack(nrec, next_).tobytes() == packed.tobytes()                            # (b)
     old = orc.columns(arena, offs, lens, orec)
@@ -214,12 +239,7 @@ def run_rewrite(zp, arena, offs, lens, cols, base=0, stream=None):
     for name, _, _ in orc.COLUMN_SPEC:                                                     # (c)
         if name in cols:
             m = applied[name]
-            wr = cols[name]
-            if name in ("src_addr", "dest_addr"):       # IPv4: bytes 0-3, the rest reads 0
-                wr = wr.copy()
-                wr[(orec["flags"] & 4) != 0, 4:] = 0
-            elif name == "ip_id":                       # 16 bits of IPv4 id, 20 of flow label
-                wr = np.where((orec["flags"] & 4) != 0, wr & 0xFFFF, wr & 0xFFFFF).astype(wr.dtype)
+            wr = as_extracted(name, cols[name], orec)
             assert np.array_equal(new[name][m], wr[m]), name
             assert np.array_equal(new[name][~m], old[name][~m]), name
         elif name != "l4_checksum":
@@ -460,5 +480,157 @@ def test_gpu_rewrite_stream_and_facade_checks(zp):
     o2[1] = o2[0]                                       # frames 0 and 1 overlap
     with pytest.raises(ValueError):
         zp.columns.rewrite(a, o2, l_, recs, {"ttl": ttl})
+    torch.cuda.synchronize()
+    assert torch.equal(a, before)
+
+
+# ---- GPU: layouts, reuse of records, capture, overlap checks ---------------
+
+def to_device(arena, offs, lens):
+    import torch
+    d = torch.device("cuda:0")
+    return (torch.from_numpy(arena).to(d), torch.from_numpy(offs.astype(np.int64)).to(d),
+            torch.from_numpy(lens.astype(np.int32)).to(d))
+
+
+def tcp6_bare():
+    """Ethernet / IPv6 / TCP without payload: 74 B, the TCP header's last
+    byte is the frame's last."""
+    f = repair(_eth(0x86DD) + _ip6(6, _tcp(4000, 443, b"")))
+    assert len(f) == 74 and orc.parse_one(f)[0] == 0
+    return f
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["gapped", "reversed", "shuffled", "tight_end"])
+def test_gpu_rewrite_layouts(zp, layout):
+    """The ABI puts frames anywhere: 700 c5 frames with 1-23 bytes of non-zero
+    filler between them (which must survive), the descriptors ascending,
+    reversed or shuffled; and a back-to-back batch whose last frame, a 74-B
+    TCP/IPv6 segment without payload, ends on the allocation's last byte."""
+    ha, ho, hl = zp.batch.generate_host("c5", 700, first=31)
+    frames = [ha[int(o):int(o) + int(l)].tobytes() for o, l in zip(ho, hl)]
+    rng = np.random.default_rng(17)
+    tight = layout == "tight_end"
+    if tight:
+        frames.append(tcp6_bare())
+    gaps = np.zeros(len(frames), np.int64) if tight else rng.integers(1, 24, len(frames))
+    lens = np.array([len(f) for f in frames], np.uint32)
+    offs = (np.cumsum(gaps) + np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.int64)])
+            ).astype(np.uint64)
+    end = int(offs[-1] + lens[-1])
+    arena = rng.integers(1, 256, end + (0 if tight else 9), dtype=np.uint8)
+    owned = np.zeros(len(arena), bool)
+    for o, f in zip(offs, frames):
+        arena[int(o):int(o) + len(f)] = np.frombuffer(f, np.uint8)
+        owned[int(o):int(o) + len(f)] = True
+    if layout == "reversed":
+        offs, lens = offs[::-1].copy(), lens[::-1].copy()
+    elif layout == "shuffled":
+        p = rng.permutation(len(offs))
+        offs, lens = offs[p], lens[p]
+    assert (frames_at(offs, lens, offs.astype(np.int64) + 5) == np.arange(len(offs))).all()
+    cols = random_cols(np.random.default_rng(23), len(offs), WRITABLE)
+    got, changed, orec = run_rewrite(zp, arena, offs, lens, cols, guard=0 if tight else 64)
+    assert (orec["err"] == 0).all() and all(changed[k].any() for k in WRITABLE)
+    assert tight or ((~owned).sum() > 700 and np.array_equal(got[~owned], arena[~owned])
+                     and got[~owned].all())
+    if tight:
+        assert int(offs[-1] + lens[-1]) == len(arena) and lens[-1] == 74
+        assert all(changed[k][-1] for k in ("src_port", "tcp_window", "src_addr"))
+
+
+@pytest.mark.gpu
+def test_gpu_rewrite_reuses_records(zp):
+    """Semantics 5, three times over: successive rewrites of one c6 batch with
+    the records of the one parse (all 14 columns, the NAT set, the ports),
+    each equal to rewrite_ref applied in turn; a GPU parse afterwards gives
+    the original records, and a GPU extract the last-written values."""
+    import torch
+    arena, offs, lens = zp.batch.generate_host("c6", 2000, first=3)
+    orec, oext = orc.parse_batch(arena, offs, lens)
+    a, o, l_ = to_device(arena, offs, lens)
+    recs, _ = zp.batch.parse_batch(a, o, l_)
+    packed = orc.pack(orec, oext).tobytes()
+    assert recs.cpu().numpy().tobytes() == packed
+    want, last = arena, {}
+    for k, names in enumerate([WRITABLE, NAT, ("src_port", "dest_port")]):
+        cols = random_cols(np.random.default_rng(70 + k), len(offs), names)
+        zp.columns.rewrite(a, o, l_, recs, {c: torch.from_numpy(v).to(a.device)
+                                            for c, v in cols.items()})
+        want, changed, applied = rewrite_batch_ref(want, offs, lens, orec, oext, cols)
+        bad = np.nonzero(a.cpu().numpy() != want)[0]
+        assert bad.size == 0, (k, bad[:8], frames_at(offs, lens, bad[:8]))
+        assert all(changed[c].any() for c in names)
+        for c in names:
+            last[c] = (as_extracted(c, cols[c], orec), applied[c])
+    recs2, _ = zp.batch.parse_batch(a, o, l_)
+    got = zp.columns.extract(a, o, l_, recs2, names=list(WRITABLE))
+    torch.cuda.synchronize()
+    assert recs2.cpu().numpy().tobytes() == packed
+    assert torch.equal(recs, recs2)                       # and the rewrite left its input alone
+    for c, (wr, m) in last.items():
+        assert m.any() and np.array_equal(got[c].cpu().numpy()[m], wr[m]), c
+
+
+@pytest.mark.gpu
+def test_gpu_rewrite_check_false_under_capture(zp):
+    """columns.rewrite(check=False) neither reduces nor synchronises, so one
+    torch.cuda.graph holds it (a single kernel); replayed twice with the
+    column tensors edited in place in between, the arena is rewrite_ref
+    applied twice."""
+    import torch
+    arena, offs, lens = zp.batch.generate_host("c5", 1500, first=44)
+    orec, oext = orc.parse_batch(arena, offs, lens)
+    a, o, l_ = to_device(arena, offs, lens)
+    recs, _ = zp.batch.parse_batch(a, o, l_)
+    first = random_cols(np.random.default_rng(91), 1500, NAT)
+    second = random_cols(np.random.default_rng(92), 1500, NAT)
+    tc = {c: torch.from_numpy(v).to(a.device) for c, v in first.items()}
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        zp.columns.rewrite(a, o, l_, recs, tc, check=False)
+    torch.cuda.synchronize()
+    assert np.array_equal(a.cpu().numpy(), arena)         # capturing ran nothing
+    g.replay()
+    torch.cuda.synchronize()
+    want, _, _ = rewrite_batch_ref(arena, offs, lens, orec, oext, first)
+    assert np.array_equal(a.cpu().numpy(), want)
+    for c, v in second.items():
+        tc[c].copy_(torch.from_numpy(v))
+    g.replay()
+    torch.cuda.synchronize()
+    want2, changed, _ = rewrite_batch_ref(want, offs, lens, orec, oext, second)
+    assert np.array_equal(a.cpu().numpy(), want2) and all(c.any() for c in changed.values())
+
+
+@pytest.mark.gpu
+def test_gpu_rewrite_disjoint_edges(zp):
+    """columns.rewrite's overlap check: frames that touch are accepted; a
+    one-byte overlap, a frame inside another and a duplicate descriptor raise
+    ValueError before anything is written."""
+    import torch
+    arena, offs, lens = zp.batch.generate_host("c5", 300, first=12)
+    assert (np.diff(offs.astype(np.int64)) == lens[:-1]).all()           # every pair touches
+    cols = random_cols(np.random.default_rng(3), 300, NAT)
+    run_rewrite(zp, arena, offs, lens, cols)
+    a, o, l_ = to_device(arena, offs, lens)
+    recs, _ = zp.batch.parse_batch(a, o, l_)
+    tc = {c: torch.from_numpy(v).to(a.device) for c, v in cols.items()}
+    before = a.clone()
+    big = int(np.argmax(lens[:-1]))
+    assert lens[big] >= 200
+    one_byte, inside, dup = o.clone(), o.clone(), o.clone()
+    one_byte[7] -= 1                                      # frame 7 starts on frame 6's last byte
+    inside[big + 1] = o[big] + 10                         # a 64-B descriptor inside frame `big`
+    l_in = l_.clone()
+    l_in[big + 1] = 64
+    dup[9] = o[8]
+    l_dup = l_.clone()
+    l_dup[9] = l_[8]
+    for oo, ll in ((one_byte, l_), (inside, l_in), (dup, l_dup)):
+        with pytest.raises(ValueError):
+            zp.columns.rewrite(a, oo, ll, recs, tc)
     torch.cuda.synchronize()
     assert torch.equal(a, before)

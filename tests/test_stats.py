@@ -62,13 +62,24 @@ def test_stats_match_oracle(zp, golden):
 @pytest.mark.gpu
 def test_stats_byte_counter_flush(zp):
     """48M synthetic records, 90 % of them with all 24 flag bits set: every
-    lane runs past the 31 trips after which zp_stats_kernel flushes its SWAR
-    byte counters (ST_GRID 512 x 256 lanes x ST_U 8 = 1M records per trip),
-    and without that flush the byte counts (> 255 per lane) would carry into
-    the next flag's byte. Counts equal numpy counts of the same records."""
+    lane runs past the trips after which zp_stats_kernel flushes its SWAR
+    byte counters (ST_GRID 512 x 256 lanes x ST_U 16 = 2M records per trip,
+    a flush once more than 255 - ST_U records are pending: after 15 trips;
+    48M records are 24 trips), and without that flush the byte counts (> 255
+    per lane) would carry into the next flag's byte. The trip counts are
+    taken from the kernel's constants. Counts equal numpy counts of the same
+    records."""
     import torch
     d = torch.device("cuda:0")
     n = 48 << 20
+    src = open(os.path.join(ROOT, "zero-packet_amd", "csrc", "zp_stats.hip")).read()
+    st = {k: int(re.search(r"#define %s (\d+)" % k, src).group(1))
+          for k in ("ST_U", "ST_GRID", "ST_BLOCK")}
+    assert "pending > 255 - ST_U" in src
+    flush_after = (255 - st["ST_U"]) // st["ST_U"] + 1       # first trip with pending > 255 - ST_U
+    per_trip = st["ST_GRID"] * st["ST_BLOCK"] * st["ST_U"]
+    assert (st["ST_U"], flush_after) == (16, 15) and flush_after * st["ST_U"] <= 255
+    assert n // per_trip > flush_after                      # whole trips of every lane
     torch.manual_seed(5)
     full = torch.rand(n, device=d) < 0.9
     flags = torch.where(full, torch.full((n,), 0xFFFFFF, dtype=torch.int64, device=d),

@@ -2,8 +2,9 @@
 // (include/zero_packet.h, zp_rewrite_columns_device): entry i of every given
 // column is written into the frame where the extract of that column would
 // read a present reader, and the IPv4 header checksum and the L4 checksum are
-// updated from the changed 16-bit words alone (RFC 1624). `rd(x)` returns the
-// frame's old byte x from wherever the caller staged it; `g` is the frame in
+// updated from the changed 16-bit words alone (RFC 1624; an L4 slice of
+// ZP_REWRITE_EXACT_L4_BYTES or more is summed in full instead). `rd(x)`
+// returns the frame's old byte x from wherever the caller staged it; `g` is the frame in
 // global memory (a pointer to uint8_t, in the global address space if the
 // caller knows it). Frames sit at any alignment and share dwords with their
 // neighbours, so every store covers exactly the bytes of its field: byte
@@ -47,13 +48,101 @@ __device__ __forceinline__ void rw_add(RwSum& s, const RwSum& d) {
 // The new checksum from the stored one: T = ~C + acc folded with end-around
 // carry, 0 counted as 0xFFFF, complemented. For a frame that verified this is
 // the writers' full recompute (T = S' mod 65535, both in
-// [1, 0xFFFF]). acc holds at most 40 words, so two folds suffice.
+// [1, 0xFFFF]) as long as the reference's u32 sum cannot wrap: every IPv4
+// header, and an L4 slice below ZP_REWRITE_EXACT_L4_BYTES. acc holds at most
+// 40 words, so two folds suffice.
 __device__ __forceinline__ uint32_t rw_checksum(uint32_t c, const RwSum& s) {
     uint32_t t = (~c & 0xFFFFu) + s.acc;
     t = (t & 0xFFFFu) + (t >> 16);
     t = (t & 0xFFFFu) + (t >> 16);
     if (t == 0) t = 0xFFFFu;
     return ~t & 0xFFFFu;
+}
+
+// The L4 checksum of a long slice (len - p >= ZP_REWRITE_EXACT_L4_BYTES), the
+// way the L4 writers' set_checksum(pseudo_sum) computes it (tcp.rs:123-129,
+// icmpv4.rs:74-80, icmpv6.rs:71-77): the full word sum of the NEW slice
+// g[p, len) with the checksum field at ck counted as zero, plus the
+// pseudo-header of the innermost IP header, in the reference's wrapping u32
+// (checksum.rs:5-29). A sum that may reach 2^32 is not a sum mod 65535 (every
+// wrap shifts the folded value by one, and a wrapped sum of 0 folds to 0), so
+// rw_checksum does not serve these frames. Called after the frame's field
+// stores, by the lane that made them; the lane alone reads its slice, in
+// aligned 16-B chunks (the bytes outside [p, len) masked out), summing the
+// bytes at even and odd addresses apart as the parse's exact path does.
+// Only an IPv6 header can sit in front of such a slice (parser.rs:203 bounds
+// an IPv4 payload by its 16-bit total length), its protocol is the L4
+// reader's (parser.rs:96-98), and UDP does not occur (parser.rs:261).
+template <class P>
+__device__ __forceinline__ uint32_t rw_l4_exact(P g, uint32_t flags, uint32_t hl, uint32_t p,
+                                                uint32_t len, uint32_t ck, uint32_t l4f,
+                                                uint32_t fallback) {
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    // the innermost IP header: the one whose payload starts at p. An accepted
+    // frame's chain has no errors, so the walk only needs the header lengths
+    // (ipv4.rs IHL; headers.rs:51-213: the five extension types, each once,
+    // Destination Options twice).
+    uint32_t pos = hl;
+    if (flags & ZP_F_IP_IN_IP) {
+        bool found = false;
+        while (!found && pos + 40u <= p) {
+            uint32_t nxt, proto;
+            if ((g[pos] >> 4) == 4) {
+                nxt = pos + (g[pos] & 15u) * 4u;
+                proto = g[pos + 9];
+            } else {
+                uint32_t pres = 0;
+                nxt = pos + 40u;
+                proto = g[pos + 6];
+                for (int it = 0; it < 7; ++it) {
+                    const uint32_t bit = proto == 0 ? 1u : proto == 43 ? 2u : proto == 44 ? 4u
+                                       : proto == 51 ? 8u
+                                       : proto == 60 ? ((pres & 16u) ? 32u : 16u) : 0u;
+                    if (bit == 0 || (pres & bit) || nxt + 8u > p) break;
+                    const uint32_t b1 = g[nxt + 1];
+                    pres |= bit;
+                    proto = g[nxt];
+                    nxt += bit == 4u ? 8u : bit == 8u ? (b1 + 2u) * 4u : (b1 + 1u) * 8u;
+                }
+            }
+            if (nxt == p && proto != 4 && proto != 41) found = true;
+            else if (nxt <= pos || nxt > p || (proto != 4 && proto != 41)) break;
+            else pos = nxt;
+        }
+        if (!found) return fallback;         // not reached for a frame the parse accepted
+    }
+    if ((g[pos] >> 4) != 6 || pos + 40u > p) return fallback;     // as above
+    uint32_t acc = (l4f == ZP_F_TCP ? 6u : l4f == ZP_F_ICMPV4 ? 1u : 58u) + (len - p);   // checksum.rs:67-69
+    for (uint32_t k = 0; k < 32; k += 2) acc += ((uint32_t)g[pos + 8 + k] << 8) | g[pos + 9 + k];
+    const uintptr_t a0 = (uintptr_t)g + p, a1 = (uintptr_t)g + len;
+    uint64_t E = 0, O = 0;                   // byte sums at even / odd addresses
+    for (uintptr_t d = a0 & ~(uintptr_t)15; d < a1; d += 16) {
+        const u32x4 q = *(const __attribute__((address_space(1))) u32x4*)d;
+        uint32_t v[4] = {q.x, q.y, q.z, q.w};
+        if (d < a0 || a1 - d < 16) {         // the slice's first and last chunk
+            const uint32_t lo = d < a0 ? (uint32_t)(a0 - d) : 0u;
+            const uint32_t hi = a1 - d < 16 ? (uint32_t)(a1 - d) : 16u;
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                uint32_t m = 0;
+#pragma unroll
+                for (uint32_t b = 0; b < 4; ++b)
+                    if (4 * k + b >= lo && 4 * k + b < hi) m |= 0xFFu << (8 * b);
+                v[k] &= m;
+            }
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            E += (v[k] & 0xFFu) + ((v[k] >> 16) & 0xFFu);
+            O += ((v[k] >> 8) & 0xFFu) + (v[k] >> 24);
+        }
+    }
+    // words start at p; the checksum field (even from p) counts as zero
+    const uint64_t W = ((a0 & 1) ? 256ull * O + E : 256ull * E + O) -
+                       (((uint32_t)g[ck] << 8) | g[ck + 1]);
+    uint32_t S = (uint32_t)(acc + W);                                  // checksum.rs:12: u32 wrap
+    while (S >> 16) S = (S & 0xFFFFu) + (S >> 16);
+    return ~S & 0xFFFFu;
 }
 
 // One big-endian 16-bit / 32-bit field at x (even from its header's start).
@@ -246,6 +335,13 @@ __device__ __forceinline__ void rewrite_frame(R& rd, P g, uint32_t flags, uint32
         if (tcp && c.p[ZP_COL_TCP_WINDOW]) put16(rd, g, p + 14, wnd, s4);    // tcp.rs:87
         // tcp.rs:123-129, udp.rs:65-71, icmpv4.rs:74-80, icmpv6.rs:71-77
         const uint32_t ck = p + (tcp ? 16u : udp ? 6u : 2u);
-        if (s4.chg) st_be16(g, ck, rw_checksum(rd16(rd, ck), s4));
+        if (s4.chg) {
+            uint32_t v = rw_checksum(rd16(rd, ck), s4);
+            // a slice long enough for the reference's u32 sum to wrap: the
+            // full recompute (rare: IPv6 jumbograms only)
+            if (__builtin_expect(len - p >= ZP_REWRITE_EXACT_L4_BYTES, 0))
+                v = rw_l4_exact(g, flags, hl, p, len, ck, l4f, v);
+            st_be16(g, ck, v);
+        }
     }
 }

@@ -11,8 +11,10 @@
 // One lane per frame, 256 frames per workgroup, the header window staged as
 // in zp_columns_kernel (zp_win.h). A frame the parse accepted has valid
 // checksums, so both are updated from the changed words alone (zp_rewrite.h)
-// and the payload is never read: per frame the header's one or two 128-B
-// lines in, the written bytes out.
+// and the payload is not read: per frame the header's one or two 128-B
+// lines in, the written bytes out. The one exception is an L4 slice long
+// enough for the reference's u32 sum to wrap (ZP_REWRITE_EXACT_L4_BYTES, IPv6
+// jumbograms): its lane sums the new slice in full (rw_l4_exact).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
