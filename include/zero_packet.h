@@ -655,6 +655,109 @@ int zp_rewrite_columns_device(uint8_t* arena, const uint64_t* offs,
                               uint64_t n, const void* const* cols, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Select and gather: choose parsed frames on the device and hand them on as  */
+/* a sub-batch. A record holds frame-relative offsets, so a selected frame's  */
+/* record stays valid wherever the frame is copied: a sub-batch is the        */
+/* gathered descriptors, records and ext entries, over the same arena (a      */
+/* view) or over a freshly packed one, and every entry point above takes it.  */
+/*                                                                            */
+/* Frame i is selected when all of these hold:                                */
+/*   the record predicate over f = record flags & ZP_F_MASK and the record's  */
+/*     err: (f & flags_all) == flags_all, (f & flags_none) == 0, flags_any    */
+/*     == 0 or (f & flags_any) != 0, and err as ZP_SEL_ERR_* / a zp_err code  */
+/*     says (an error record has f == 0);                                     */
+/*   min_len <= lens[i] <= max_len;                                           */
+/*   every term. A term's value v is exactly the entry i that                 */
+/*     zp_extract_columns_device would store for its column: 0 for an error   */
+/*     record or an absent reader, an IPv4 address in bytes 0-3 with zeros    */
+/*     behind. So a selector that must tell 10.0.0.0/8 from an IPv6 address   */
+/*     whose first byte is 0x0A adds a term on ZP_COL_IP_VERSION.             */
+/* Terms are ANDed; callers who need OR run two selections and OR the masks.  */
+/* ------------------------------------------------------------------------- */
+#define ZP_SELECT_MAX_TERMS 8
+typedef enum zp_sel_op {
+    ZP_SEL_MASK_EQ = 0,   /* (v & b) == a, byte-wise over the column's width          */
+    ZP_SEL_MASK_NE = 1,   /* its negation                                             */
+    ZP_SEL_RANGE   = 2,   /* a <= v <= b, unsigned; scalar columns (width 1, 2, 4)    */
+    ZP_SEL_NOT_RANGE = 3
+} zp_sel_op;
+typedef struct zp_select_term {      /* 40 bytes */
+    uint8_t col;                     /* zp_col                                        */
+    uint8_t op;                      /* zp_sel_op                                     */
+    uint8_t pad[6];                  /* must be 0                                     */
+    uint8_t a[16], b[16];            /* in the column's own layout: LE scalars in the */
+} zp_select_term;                    /* first width bytes, byte arrays as extracted   */
+#define ZP_SEL_ERR_ANY     (-1)      /* err not looked at                             */
+#define ZP_SEL_ERR_NONZERO (-2)      /* any rejected frame                            */
+typedef struct zp_select {
+    uint32_t flags_all, flags_any, flags_none;  /* over record flags & ZP_F_MASK; flags_any 0 = ignored */
+    int32_t  err;                    /* ZP_SEL_ERR_* or a zp_err code (0 = accepted)  */
+    uint32_t min_len, max_len;       /* on lens[i], inclusive; 0 / UINT32_MAX = none  */
+    uint32_t nterms;
+    zp_select_term terms[ZP_SELECT_MAX_TERMS];   /* all must hold (AND)               */
+} zp_select;
+
+/* Frames one workgroup of the scan phase covers; a larger batch takes a
+ * second scan launch (tests cross this size). */
+#define ZP_SELECT_SCAN_FRAMES 262144u
+
+/* Bytes of device scratch zp_select_device needs for n frames. */
+uint64_t zp_select_scratch_bytes(uint64_t n);
+
+/* Marks the selected frames of a parsed batch and compacts them, stably (in
+ * ascending frame order). `sel` is host memory, everything else device
+ * memory. With c frames selected:
+ *   mask         optional, ceil(n / 64) words: bit i % 64 of word i / 64 is
+ *                frame i's verdict; bits at and past n are 0;
+ *   idx          optional, capacity n: idx[0, c) = the selected indices;
+ *   packed_offs  optional, capacity n: packed_offs[j] = the sum of lens of the
+ *                selected frames before the j-th (the back-to-back layout);
+ *   count        required, 2 words: {c, sum of the selected frames' lens}.
+ * Entries of idx / packed_offs at and past c are not written. With nterms ==
+ * 0 the frames are not read and arena / offs may be NULL; lens may then be
+ * NULL too when no length bound is set and packed_offs is NULL (count[1] is
+ * then 0). Refused with a negative value before anything is launched
+ * (zp_last_error names the cause): a null sel, count, records or scratch,
+ * nterms > ZP_SELECT_MAX_TERMS, a term with a column out of range, a nonzero
+ * pad, an unknown op or RANGE / NOT_RANGE on a byte-array column, terms
+ * without arena / offs / lens, n >= 2^32 with idx, scratch_bytes below
+ * zp_select_scratch_bytes(n). n == 0 writes count = {0, 0} and returns 0.
+ * Three kernel launches on `stream` (mark, scan, scatter; the scatter only
+ * when idx or packed_offs is given): nothing is allocated and nothing waits,
+ * so the call captures into a graph. */
+int zp_select_device(const uint8_t* arena, const uint64_t* offs, const uint32_t* lens,
+                     const zp_record* records, uint64_t n, const zp_select* sel /* host */,
+                     uint64_t* mask,        /* optional: ceil(n/64) words, bit i%64 of word i/64 */
+                     uint32_t* idx,         /* optional: n entries capacity                      */
+                     uint64_t* packed_offs, /* optional: n entries capacity                      */
+                     uint64_t* count,       /* required: 2 device words {selected, sum of lens}  */
+                     void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* Gathers the first min(m, *count) entries of idx into a sub-batch (m: the
+ * host's bound, it sizes the grid; count == NULL: m). Entry j is frame idx[j]:
+ *   out_lens[j], out_records[j], out_ext[j] / out_ext[m + j]: element gathers
+ *   (each optional; an ext entry is copied whether or not its record flags a
+ *   chain);
+ *   dst == NULL: out_offs[j] = offs[idx[j]], a view over the same arena;
+ *   dst: the frame's lens bytes go to dst + packed_offs[j] and out_offs[j] =
+ *   packed_offs[j]. packed_offs is what zp_select_device wrote (ascending,
+ *   back to back). Exactly the frames' bytes are written, nothing between or
+ *   around them and nothing outside [dst, dst + dst_bytes): a frame that does
+ *   not fit is not copied. dst must not overlap the arena. dst_bytes / m,
+ *   the average frame dst was sized for, also picks how many entries a
+ *   workgroup takes; it changes speed only.
+ * Source reads stay inside the 16-B chunks that hold a frame's bytes, as the
+ * parse's do. One launch on `stream`; enqueue-only. */
+int zp_gather_frames_device(const uint8_t* arena, const uint64_t* offs, const uint32_t* lens,
+                            const zp_record* records, const zp_ext_offsets* ext /* opt, 2n */,
+                            uint64_t n, const uint32_t* idx, const uint64_t* packed_offs,
+                            uint64_t m, const uint64_t* count /* optional device word */,
+                            uint8_t* dst /* NULL: a view, no frame is copied */, uint64_t dst_bytes,
+                            uint64_t* out_offs, uint32_t* out_lens, zp_record* out_records,
+                            zp_ext_offsets* out_ext /* opt, 2m: [j] outer, [m + j] inner */,
+                            void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Batched PacketBuilder. The reference builds one    */
 /* frame with a typestate chain over a caller-sized buffer                    */
 /* (builder.rs:55-909): PacketBuilder::new(&mut buf).ethernet(..).ipv4(..)    */

@@ -603,6 +603,108 @@ inline void rewrite_columns(uint8_t* arena, const uint64_t* offs, const uint32_t
         throw std::runtime_error(std::string("zp_rewrite_columns_device: ") + zp_last_error());
 }
 
+// A selector for zp::select (zp_select, zero_packet.h): the record predicate,
+// the length bounds and up to ZP_SELECT_MAX_TERMS column terms, all ANDed.
+//   zp::Select().ok().has(ZP_F_TCP).between(ZP_COL_DEST_PORT, 1024, 65535)
+//       .prefix(ZP_COL_SRC_ADDR, {10, 0, 0, 0}, 8).eq(ZP_COL_IP_VERSION, 4)
+// A term's value is the column entry zp_extract_columns_device would store
+// (an IPv4 address in bytes 0-3 with zeros behind: pair a short IPv4 prefix
+// with a term on ZP_COL_IP_VERSION). Scalar operands are host integers, byte
+// arrays (MACs, addresses) the bytes as extracted.
+class Select {
+public:
+    Select() {
+        std::memset(&s_, 0, sizeof s_);
+        s_.err = ZP_SEL_ERR_ANY;
+        s_.max_len = UINT32_MAX;
+    }
+    Select& ok(bool accepted = true) { s_.err = accepted ? 0 : ZP_SEL_ERR_NONZERO; return *this; }
+    Select& err(int code) { s_.err = code; return *this; }
+    Select& has(uint32_t flags) { s_.flags_all |= flags; return *this; }
+    Select& lacks(uint32_t flags) { s_.flags_none |= flags; return *this; }
+    Select& any_of(uint32_t flags) { s_.flags_any |= flags; return *this; }
+    Select& len(uint32_t min_len, uint32_t max_len = UINT32_MAX) {
+        s_.min_len = min_len;
+        s_.max_len = max_len;
+        return *this;
+    }
+    Select& eq(zp_col col, uint64_t v) { return scalar(col, ZP_SEL_MASK_EQ, v, ~0ull); }
+    Select& ne(zp_col col, uint64_t v) { return scalar(col, ZP_SEL_MASK_NE, v, ~0ull); }
+    Select& mask_eq(zp_col col, uint64_t v, uint64_t mask) { return scalar(col, ZP_SEL_MASK_EQ, v, mask); }
+    Select& mask_ne(zp_col col, uint64_t v, uint64_t mask) { return scalar(col, ZP_SEL_MASK_NE, v, mask); }
+    Select& between(zp_col col, uint64_t lo, uint64_t hi) { return scalar(col, ZP_SEL_RANGE, lo, hi); }
+    Select& outside(zp_col col, uint64_t lo, uint64_t hi) { return scalar(col, ZP_SEL_NOT_RANGE, lo, hi); }
+    // Byte-array columns: (v & mask) == value over the column's width.
+    Select& bytes_eq(zp_col col, const uint8_t* value, const uint8_t* mask, size_t n,
+                     bool negate = false) {
+        if (n > 16 || zp_col_width(col) != (int)n || n <= 4)
+            throw std::invalid_argument("zp::Select: operand width is not the byte-array column's");
+        zp_select_term& t = next(col, negate ? ZP_SEL_MASK_NE : ZP_SEL_MASK_EQ);
+        std::memcpy(t.a, value, n);
+        if (mask) std::memcpy(t.b, mask, n);
+        else std::memset(t.b, 0xFF, n);
+        return *this;
+    }
+    Select& mac(zp_col col, const std::array<uint8_t, 6>& m) { return bytes_eq(col, m.data(), nullptr, 6); }
+    // An IPv4 (4 address bytes) or IPv6 (16) prefix of `bits` bits.
+    template <size_t N>
+    Select& prefix(zp_col col, const std::array<uint8_t, N>& addr, unsigned bits) {
+        static_assert(N == 4 || N == 16, "an IPv4 or IPv6 address");
+        if (bits > 8 * N) throw std::invalid_argument("zp::Select: prefix longer than the address");
+        uint8_t a[16] = {0}, m[16] = {0};
+        for (size_t k = 0; k < N; ++k) {
+            const unsigned left = bits > 8 * k ? bits - 8 * (unsigned)k : 0;
+            m[k] = left >= 8 ? 0xFF : (uint8_t)(0xFF00u >> left);
+            a[k] = addr[k] & m[k];
+        }
+        return bytes_eq(col, a, m, 16);
+    }
+    const zp_select& get() const { return s_; }
+
+private:
+    zp_select_term& next(zp_col col, int op) {
+        if (s_.nterms >= ZP_SELECT_MAX_TERMS) throw std::invalid_argument("zp::Select: too many terms");
+        zp_select_term& t = s_.terms[s_.nterms++];
+        t.col = (uint8_t)col;
+        t.op = (uint8_t)op;
+        return t;
+    }
+    Select& scalar(zp_col col, int op, uint64_t a, uint64_t b) {
+        const int w = zp_col_width(col);
+        if (w != 1 && w != 2 && w != 4) throw std::invalid_argument("zp::Select: not a scalar column");
+        const uint64_t top = (1ull << (8 * w)) - 1;
+        if (a > top || (b > top && b != ~0ull)) throw std::invalid_argument("zp::Select: operand does not fit the column");
+        zp_select_term& t = next(col, op);
+        for (int k = 0; k < w; ++k) {
+            t.a[k] = (uint8_t)(a >> (8 * k));
+            t.b[k] = (uint8_t)(b >> (8 * k));
+        }
+        return *this;
+    }
+    zp_select s_;
+};
+
+// zp_select_device / zp_gather_frames_device (zero_packet.h): enqueue-only on
+// `stream`; a refusal throws with zp_last_error's text.
+inline void select(const uint8_t* arena, const uint64_t* offs, const uint32_t* lens,
+                   const zp_record* records, uint64_t n, const Select& sel, uint64_t* mask,
+                   uint32_t* idx, uint64_t* packed_offs, uint64_t* count, void* scratch,
+                   uint64_t scratch_bytes, void* stream) {
+    if (zp_select_device(arena, offs, lens, records, n, &sel.get(), mask, idx, packed_offs, count,
+                         scratch, scratch_bytes, stream) < 0)
+        throw std::runtime_error(std::string("zp_select_device: ") + zp_last_error());
+}
+inline void gather_frames(const uint8_t* arena, const uint64_t* offs, const uint32_t* lens,
+                          const zp_record* records, const zp_ext_offsets* ext, uint64_t n,
+                          const uint32_t* idx, const uint64_t* packed_offs, uint64_t m,
+                          const uint64_t* count, uint8_t* dst, uint64_t dst_bytes,
+                          uint64_t* out_offs, uint32_t* out_lens, zp_record* out_records,
+                          zp_ext_offsets* out_ext, void* stream) {
+    if (zp_gather_frames_device(arena, offs, lens, records, ext, n, idx, packed_offs, m, count, dst,
+                                dst_bytes, out_offs, out_lens, out_records, out_ext, stream) < 0)
+        throw std::runtime_error(std::string("zp_gather_frames_device: ") + zp_last_error());
+}
+
 // Per-batch counters (zp_stats_device): adds into counts[ZP_STATS_COUNT].
 inline void stats_device(const zp_record* records, uint64_t n, uint64_t* counts, void* stream) {
     if (zp_stats_device(records, n, counts, stream) < 0)

@@ -98,11 +98,42 @@ __device__ __forceinline__ void col_mac(const ColPtrs& c, int col, uint64_t i, R
     d[2] = (uint16_t)rd_le(rd, x + 4, 2);
 }
 
-// Writes entry i of every requested column for one frame: record r (ok =
-// parsed without error, with an Ethernet reader), frame length len.
-template <class R>
-__device__ __forceinline__ void emit_columns(R& rd, const zp_rec_full& r, bool ok, uint32_t len,
-                                             uint64_t i, const ColPtrs& c) {
+// Where the values of one frame's columns go. col_values() below walks the
+// getters once and hands every column to a sink S:
+//   s.mac(col, rd, x) / s.addr(col, rd, x, v6)   a byte-array column of a present reader,
+//                                                read at frame byte x
+//   s.put(col, v)                                a scalar column (always called; 0: absent)
+//   s.l3() / s.inner() / s.l4()                  whether any column of the outer IP (and ARP) /
+//                                                ip_in_ip / L4 group is wanted: a group that
+//                                                is not wanted is not read from the frame
+// A byte-array column whose reader is absent is all zero and gets no call: a
+// sink starts from that value. The one sink that cannot is ColStore (S::kStore),
+// the column kernels' sink, which has to write the zero entry i of every
+// requested column: col_values() keeps those stores as the statements over
+// s.c / s.i that the column kernels always had, and reads every group for it.
+// zp_select.hip's sink evaluates selector terms on the same values instead.
+struct ColStore {
+    const ColPtrs& c;
+    uint64_t i;
+    static constexpr bool kStore = true;
+    static __device__ __forceinline__ bool l3() { return true; }
+    static __device__ __forceinline__ bool inner() { return true; }
+    static __device__ __forceinline__ bool l4() { return true; }
+    template <class R>
+    __device__ __forceinline__ void mac(int col, R& rd, uint32_t x) { col_mac(c, col, i, rd, x); }
+    template <class R>
+    __device__ __forceinline__ void addr(int col, R& rd, uint32_t x, bool v6) {
+        col_addr(c, col, i, rd, x, v6);
+    }
+    template <typename T>
+    __device__ __forceinline__ void put(int col, T v) { st<T>(c, col, i, v); }
+};
+
+// The value of every column of one frame, handed to the sink s: record r (ok
+// = parsed without error, with an Ethernet reader), frame length len.
+template <class R, class S>
+__device__ __forceinline__ void col_values(R& rd, const zp_rec_full& r, bool ok, uint32_t len,
+                                           S& s) {
     // Absent readers / errors read 0.
     uint8_t ipv = 0, proto = 0, ttl = 0, tos = 0, iv = 0, iproto = 0, l4p = 0, tflags = 0;
     uint8_t ity = 0, icode = 0;
@@ -112,8 +143,8 @@ __device__ __forceinline__ void emit_columns(R& rd, const zp_rec_full& r, bool o
     const uint4 z = make_uint4(0, 0, 0, 0);
     if (ok) {
         const uint32_t hl = r.eth_len;
-        col_mac(c, ZP_COL_DEST_MAC, i, rd, 0);                          // ethernet.rs:195-198
-        col_mac(c, ZP_COL_SRC_MAC, i, rd, 6);                           // ethernet.rs:201-204
+        s.mac(ZP_COL_DEST_MAC, rd, 0);                          // ethernet.rs:195-198
+        s.mac(ZP_COL_SRC_MAC, rd, 6);                           // ethernet.rs:201-204
         ety = (uint16_t)rd16(rd, hl - 2);                              // ethernet.rs:209-212
         const uint32_t tp = rd16(rd, 12);
         if (tp == 0x8100) tci = (uint16_t)rd16(rd, 14);                // ethernet.rs:218-229
@@ -121,12 +152,12 @@ __device__ __forceinline__ void emit_columns(R& rd, const zp_rec_full& r, bool o
             tci = (uint16_t)rd16(rd, 14);
             tci2 = (uint16_t)rd16(rd, 18);
         }
-        if (r.flags & ZP_F_ARP) oper = (uint16_t)rd16(rd, hl + 6);     // arp.rs:174-177
-        if (r.flags & (ZP_F_IPV4 | ZP_F_IPV6)) {
+        if ((S::kStore || s.l3()) && (r.flags & ZP_F_ARP)) oper = (uint16_t)rd16(rd, hl + 6);     // arp.rs:174-177
+        if ((S::kStore || s.l3()) && (r.flags & (ZP_F_IPV4 | ZP_F_IPV6))) {
             const bool v6 = (r.flags & ZP_F_IPV6) != 0;
             ipv = (uint8_t)(rd(hl) >> 4);                          // ipv4.rs:148 / ipv6.rs:173
-            col_addr(c, ZP_COL_SRC_ADDR, i, rd, hl + (v6 ? 8 : 12), v6);
-            col_addr(c, ZP_COL_DEST_ADDR, i, rd, hl + (v6 ? 24 : 16), v6);
+            s.addr(ZP_COL_SRC_ADDR, rd, hl + (v6 ? 8 : 12), v6);
+            s.addr(ZP_COL_DEST_ADDR, rd, hl + (v6 ? 24 : 16), v6);
             if (!v6) {
                 proto = (uint8_t)rd(hl + 9);                       // ipv4.rs:204-207
                 ttl = (uint8_t)rd(hl + 8);                         // ipv4.rs:198-201
@@ -141,23 +172,23 @@ __device__ __forceinline__ void emit_columns(R& rd, const zp_rec_full& r, bool o
                 ipid = ((b1 & 0x0F) << 16) | rd16(rd, hl + 2);         // ipv6.rs:189-196
                 iplen = (uint16_t)rd16(rd, hl + 4);                    // ipv6.rs:199-202
             }
-        } else {
-            if (c.p[ZP_COL_SRC_ADDR]) ((uint4*)c.p[ZP_COL_SRC_ADDR])[i] = z;
-            if (c.p[ZP_COL_DEST_ADDR]) ((uint4*)c.p[ZP_COL_DEST_ADDR])[i] = z;
+        } else if constexpr (S::kStore) {
+            if (s.c.p[ZP_COL_SRC_ADDR]) ((uint4*)s.c.p[ZP_COL_SRC_ADDR])[s.i] = z;
+            if (s.c.p[ZP_COL_DEST_ADDR]) ((uint4*)s.c.p[ZP_COL_DEST_ADDR])[s.i] = z;
         }
-        if (r.flags & ZP_F_IP_IN_IP) {
+        if ((S::kStore || s.inner()) && (r.flags & ZP_F_IP_IN_IP)) {
             const bool v6 = (r.flags & ZP_F_IP_IN_IP_V6) != 0;
             const uint32_t p = r.inner_off;
             iv = (uint8_t)(rd(p) >> 4);
-            col_addr(c, ZP_COL_INNER_SRC_ADDR, i, rd, p + (v6 ? 8 : 12), v6);
-            col_addr(c, ZP_COL_INNER_DEST_ADDR, i, rd, p + (v6 ? 24 : 16), v6);
+            s.addr(ZP_COL_INNER_SRC_ADDR, rd, p + (v6 ? 8 : 12), v6);
+            s.addr(ZP_COL_INNER_DEST_ADDR, rd, p + (v6 ? 24 : 16), v6);
             iproto = v6 ? r.inner_final_nh : (uint8_t)rd(p + 9);
-        } else {
-            if (c.p[ZP_COL_INNER_SRC_ADDR]) ((uint4*)c.p[ZP_COL_INNER_SRC_ADDR])[i] = z;
-            if (c.p[ZP_COL_INNER_DEST_ADDR]) ((uint4*)c.p[ZP_COL_INNER_DEST_ADDR])[i] = z;
+        } else if constexpr (S::kStore) {
+            if (s.c.p[ZP_COL_INNER_SRC_ADDR]) ((uint4*)s.c.p[ZP_COL_INNER_SRC_ADDR])[s.i] = z;
+            if (s.c.p[ZP_COL_INNER_DEST_ADDR]) ((uint4*)s.c.p[ZP_COL_INNER_DEST_ADDR])[s.i] = z;
         }
         const uint32_t l4f = r.flags & (ZP_F_TCP | ZP_F_UDP | ZP_F_ICMPV4 | ZP_F_ICMPV6);
-        if (l4f) {
+        if ((S::kStore || s.l4()) && l4f) {
             const uint32_t p = r.l4_off;
             uint32_t hlen = 8;
             if (l4f == ZP_F_TCP) {
@@ -185,41 +216,49 @@ __device__ __forceinline__ void emit_columns(R& rd, const zp_rec_full& r, bool o
             }
             if (hlen <= len - p) poff = p + hlen;                     // tcp.rs:235-243
         }
-    } else {
-        if (c.p[ZP_COL_DEST_MAC]) {
-            uint16_t* d = (uint16_t*)(c.p[ZP_COL_DEST_MAC] + 6 * i);
+    } else if constexpr (S::kStore) {
+        if (s.c.p[ZP_COL_DEST_MAC]) {
+            uint16_t* d = (uint16_t*)(s.c.p[ZP_COL_DEST_MAC] + 6 * s.i);
             d[0] = 0; d[1] = 0; d[2] = 0;
         }
-        if (c.p[ZP_COL_SRC_MAC]) {
-            uint16_t* d = (uint16_t*)(c.p[ZP_COL_SRC_MAC] + 6 * i);
+        if (s.c.p[ZP_COL_SRC_MAC]) {
+            uint16_t* d = (uint16_t*)(s.c.p[ZP_COL_SRC_MAC] + 6 * s.i);
             d[0] = 0; d[1] = 0; d[2] = 0;
         }
-        if (c.p[ZP_COL_SRC_ADDR]) ((uint4*)c.p[ZP_COL_SRC_ADDR])[i] = z;
-        if (c.p[ZP_COL_DEST_ADDR]) ((uint4*)c.p[ZP_COL_DEST_ADDR])[i] = z;
-        if (c.p[ZP_COL_INNER_SRC_ADDR]) ((uint4*)c.p[ZP_COL_INNER_SRC_ADDR])[i] = z;
-        if (c.p[ZP_COL_INNER_DEST_ADDR]) ((uint4*)c.p[ZP_COL_INNER_DEST_ADDR])[i] = z;
+        if (s.c.p[ZP_COL_SRC_ADDR]) ((uint4*)s.c.p[ZP_COL_SRC_ADDR])[s.i] = z;
+        if (s.c.p[ZP_COL_DEST_ADDR]) ((uint4*)s.c.p[ZP_COL_DEST_ADDR])[s.i] = z;
+        if (s.c.p[ZP_COL_INNER_SRC_ADDR]) ((uint4*)s.c.p[ZP_COL_INNER_SRC_ADDR])[s.i] = z;
+        if (s.c.p[ZP_COL_INNER_DEST_ADDR]) ((uint4*)s.c.p[ZP_COL_INNER_DEST_ADDR])[s.i] = z;
     }
-    st<uint16_t>(c, ZP_COL_ETHERTYPE, i, ety);
-    st<uint16_t>(c, ZP_COL_VLAN_TCI, i, tci);
-    st<uint16_t>(c, ZP_COL_VLAN_INNER_TCI, i, tci2);
-    st<uint16_t>(c, ZP_COL_ARP_OPER, i, oper);
-    st<uint8_t>(c, ZP_COL_IP_VERSION, i, ipv);
-    st<uint8_t>(c, ZP_COL_PROTOCOL, i, proto);
-    st<uint8_t>(c, ZP_COL_TTL, i, ttl);
-    st<uint8_t>(c, ZP_COL_TOS, i, tos);
-    st<uint32_t>(c, ZP_COL_IP_ID, i, ipid);
-    st<uint16_t>(c, ZP_COL_IP_LEN, i, iplen);
-    st<uint8_t>(c, ZP_COL_INNER_VERSION, i, iv);
-    st<uint8_t>(c, ZP_COL_INNER_PROTOCOL, i, iproto);
-    st<uint8_t>(c, ZP_COL_L4_PROTO, i, l4p);
-    st<uint16_t>(c, ZP_COL_SRC_PORT, i, sport);
-    st<uint16_t>(c, ZP_COL_DEST_PORT, i, dport);
-    st<uint32_t>(c, ZP_COL_TCP_SEQ, i, seq);
-    st<uint32_t>(c, ZP_COL_TCP_ACK, i, ack);
-    st<uint8_t>(c, ZP_COL_TCP_FLAGS, i, tflags);
-    st<uint16_t>(c, ZP_COL_TCP_WINDOW, i, win16);
-    st<uint8_t>(c, ZP_COL_ICMP_TYPE, i, ity);
-    st<uint8_t>(c, ZP_COL_ICMP_CODE, i, icode);
-    st<uint16_t>(c, ZP_COL_L4_CHECKSUM, i, l4ck);
-    st<uint32_t>(c, ZP_COL_PAYLOAD_OFF, i, poff);
+    s.put(ZP_COL_ETHERTYPE, ety);
+    s.put(ZP_COL_VLAN_TCI, tci);
+    s.put(ZP_COL_VLAN_INNER_TCI, tci2);
+    s.put(ZP_COL_ARP_OPER, oper);
+    s.put(ZP_COL_IP_VERSION, ipv);
+    s.put(ZP_COL_PROTOCOL, proto);
+    s.put(ZP_COL_TTL, ttl);
+    s.put(ZP_COL_TOS, tos);
+    s.put(ZP_COL_IP_ID, ipid);
+    s.put(ZP_COL_IP_LEN, iplen);
+    s.put(ZP_COL_INNER_VERSION, iv);
+    s.put(ZP_COL_INNER_PROTOCOL, iproto);
+    s.put(ZP_COL_L4_PROTO, l4p);
+    s.put(ZP_COL_SRC_PORT, sport);
+    s.put(ZP_COL_DEST_PORT, dport);
+    s.put(ZP_COL_TCP_SEQ, seq);
+    s.put(ZP_COL_TCP_ACK, ack);
+    s.put(ZP_COL_TCP_FLAGS, tflags);
+    s.put(ZP_COL_TCP_WINDOW, win16);
+    s.put(ZP_COL_ICMP_TYPE, ity);
+    s.put(ZP_COL_ICMP_CODE, icode);
+    s.put(ZP_COL_L4_CHECKSUM, l4ck);
+    s.put(ZP_COL_PAYLOAD_OFF, poff);
+}
+
+// Writes entry i of every requested column for one frame.
+template <class R>
+__device__ __forceinline__ void emit_columns(R& rd, const zp_rec_full& r, bool ok, uint32_t len,
+                                             uint64_t i, const ColPtrs& c) {
+    ColStore s{c, i};
+    col_values(rd, r, ok, len, s);
 }
