@@ -758,6 +758,99 @@ int zp_gather_frames_device(const uint8_t* arena, const uint64_t* offs, const ui
                             void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Flow table: group parsed frames by key on the device, with per-flow        */
+/* counters. zp_stats_device counts per batch; this counts per key.           */
+/*                                                                            */
+/* Keyed frames. Frame i is keyed when its record has err == 0 and an outer   */
+/*   IPv4 or IPv6 reader, and, if `mask` (the words zp_select_device writes)  */
+/*   is given, bit i % 64 of mask[i / 64] is set. Every other frame is not    */
+/*   keyed: its flow_of[i] is ZP_FLOW_NONE and it contributes to nothing.     */
+/* Key. The 40-byte zp_flow_key, built only from the entries                  */
+/*   zp_extract_columns_device would store for that frame: the outer IP       */
+/*   addresses (IPv4 in bytes 0-3, zeros behind) and ip_version always;       */
+/*   key_flags picks the ports (ZP_FLOW_PORTS; 0 without TCP / UDP), l4_proto */
+/*   (ZP_FLOW_PROTO) and the VLAN id, ZP_COL_VLAN_TCI & 0x0FFF                */
+/*   (ZP_FLOW_VLAN); a field that is not picked is 0. The 5-tuple is          */
+/*   ZP_FLOW_PORTS | ZP_FLOW_PROTO. ip_version is part of the key, so         */
+/*   10.0.0.1 and the IPv6 address 0a00:0001:: are different flows. Under     */
+/*   ip_in_ip the key holds the OUTER addresses and the INNERMOST L4 ports    */
+/*   and l4_proto, exactly as the columns do.                                 */
+/* ZP_FLOW_BIDIR. Both directions are one flow: if (src_addr bytes, then      */
+/*   src_port as a number) is greater than (dest_addr bytes, dest_port),      */
+/*   compared lexicographically, the two endpoints are swapped in the key     */
+/*   (the ports are compared as the key holds them: 0 without ZP_FLOW_PORTS). */
+/*   Equal endpoints stay as they are.                                        */
+/* Flow numbering. With F distinct keys among the keyed frames, flows are     */
+/*   numbered 0..F-1 in ascending order of their first frame (the smallest i  */
+/*   that has the key). The table is filled in whatever order the hardware    */
+/*   runs the frames; this numbering makes every output deterministic.        */
+/* ------------------------------------------------------------------------- */
+#define ZP_FLOW_PORTS 1u
+#define ZP_FLOW_PROTO 2u
+#define ZP_FLOW_VLAN  4u
+#define ZP_FLOW_BIDIR 8u
+#define ZP_FLOW_NONE  0xFFFFFFFFu
+typedef struct zp_flow_key {         /* 40 bytes */
+    uint8_t  src_addr[16], dest_addr[16];   /* ZP_COL_SRC_ADDR / ZP_COL_DEST_ADDR            */
+    uint16_t src_port, dest_port;    /* ZP_COL_SRC_PORT / ZP_COL_DEST_PORT   ZP_FLOW_PORTS   */
+    uint8_t  l4_proto;               /* ZP_COL_L4_PROTO                      ZP_FLOW_PROTO   */
+    uint8_t  ip_version;             /* ZP_COL_IP_VERSION, always part of the key            */
+    uint16_t vlan;                   /* ZP_COL_VLAN_TCI & 0x0FFF             ZP_FLOW_VLAN    */
+} zp_flow_key;
+typedef struct zp_flow_entry {       /* 64 bytes */
+    zp_flow_key key;
+    uint32_t first, last;            /* the flow's first and last frame index                */
+    uint32_t packets;
+    uint8_t  tcp_flags;              /* OR of ZP_COL_TCP_FLAGS over the flow's frames        */
+    uint8_t  pad[3];                 /* 0                                                    */
+    uint64_t bytes;                  /* sum of lens                                          */
+} zp_flow_entry;
+typedef struct zp_flow_opts {        /* host memory */
+    uint32_t key_flags;              /* ZP_FLOW_*                                            */
+    uint32_t pad;                    /* must be 0                                            */
+    uint64_t max_flows;              /* capacity of `flows`, > 0                             */
+    uint64_t hash_mask;              /* UINT64_MAX. The key's hash is ANDed with it before   */
+} zp_flow_opts;                      /* any use; tests pass small values to force collisions */
+
+/* Bytes of device scratch zp_flow_aggregate_device needs: 48 B per frame (the
+ * key, its slot and TCP flags), one bit and 4 B per 256 frames for the ranking,
+ * and 8 B per slot of a table of the first power of two >= 2 * min(max_flows, n)
+ * slots (at least 64), plus less than 2 KiB. That is below 64 B per frame +
+ * 64 B per max_flows + 4,096 B. */
+uint64_t zp_flow_scratch_bytes(uint64_t n, uint64_t max_flows);
+
+/* Groups the keyed frames of a parsed batch by key. `opts` is host memory,
+ * everything else device memory:
+ *   mask     optional, ceil(n / 64) words as zp_select_device writes them;
+ *   flow_of  optional, n entries: frame i's flow number, or ZP_FLOW_NONE;
+ *   flows    required, max_flows entries: flows[f] for f < F; `first` and `last`
+ *            are frame indices, entries at and past F are not written;
+ *   count    required, 4 words: {F, keyed frames, keyed bytes, overflow}.
+ *            overflow is 1 exactly when F > max_flows; then only count[3] is
+ *            defined, and still nothing is written outside the stated
+ *            capacities.
+ * Flows are told apart by comparing the whole key, never by its hash, so the
+ * results do not depend on hash_mask. The call clears what it needs of
+ * `scratch` itself, on the stream: scratch of any prior content gives the same
+ * result. Refused with a negative value before anything is launched
+ * (zp_last_error names the cause): a null opts, records, lens, arena, offs,
+ * flows, count or scratch, unknown key_flags bits, a nonzero pad, max_flows ==
+ * 0, n >= 2^32, min(max_flows, n) > 2^30, a misaligned pointer (flows, count,
+ * mask: 8 B; flow_of: 4 B), scratch_bytes below zp_flow_scratch_bytes(n,
+ * max_flows). n == 0 writes count = {0, 0, 0, 0} and returns 0.
+ * Six kernel launches on `stream` (key, insert, mark, scan, heads, label;
+ * a second scan launch past ZP_SELECT_SCAN_FRAMES frames); nothing is allocated and nothing waits, so the call captures into a
+ * graph. */
+int zp_flow_aggregate_device(const uint8_t* arena, const uint64_t* offs, const uint32_t* lens,
+                             const zp_record* records, uint64_t n,
+                             const zp_flow_opts* opts /* host */,
+                             const uint64_t* mask /* optional */,
+                             uint32_t* flow_of /* optional: n entries */,
+                             zp_flow_entry* flows /* required: max_flows entries */,
+                             uint64_t* count /* required: 4 device words */,
+                             void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Batched PacketBuilder. The reference builds one    */
 /* frame with a typestate chain over a caller-sized buffer                    */
 /* (builder.rs:55-909): PacketBuilder::new(&mut buf).ethernet(..).ipv4(..)    */

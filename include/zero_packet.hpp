@@ -705,6 +705,43 @@ inline void gather_frames(const uint8_t* arena, const uint64_t* offs, const uint
         throw std::runtime_error(std::string("zp_gather_frames_device: ") + zp_last_error());
 }
 
+// Options for zp::flow_aggregate (zp_flow_opts, zero_packet.h): the 5-tuple
+// unless told otherwise.
+//   zp::FlowOpts(max_flows).vlan().bidir()
+class FlowOpts {
+public:
+    explicit FlowOpts(uint64_t max_flows) {
+        o_.key_flags = ZP_FLOW_PORTS | ZP_FLOW_PROTO;
+        o_.pad = 0;
+        o_.max_flows = max_flows;
+        o_.hash_mask = UINT64_MAX;
+    }
+    FlowOpts& ports(bool on = true) { return flag(ZP_FLOW_PORTS, on); }
+    FlowOpts& proto(bool on = true) { return flag(ZP_FLOW_PROTO, on); }
+    FlowOpts& vlan(bool on = true) { return flag(ZP_FLOW_VLAN, on); }
+    FlowOpts& bidir(bool on = true) { return flag(ZP_FLOW_BIDIR, on); }
+    FlowOpts& hash_mask(uint64_t m) { o_.hash_mask = m; return *this; }   // tests: forced collisions
+    const zp_flow_opts& get() const { return o_; }
+
+private:
+    FlowOpts& flag(uint32_t f, bool on) {
+        o_.key_flags = on ? o_.key_flags | f : o_.key_flags & ~f;
+        return *this;
+    }
+    zp_flow_opts o_;
+};
+
+// zp_flow_aggregate_device (zero_packet.h): enqueue-only on `stream`; a
+// refusal throws with zp_last_error's text.
+inline void flow_aggregate(const uint8_t* arena, const uint64_t* offs, const uint32_t* lens,
+                           const zp_record* records, uint64_t n, const FlowOpts& opts,
+                           const uint64_t* mask, uint32_t* flow_of, zp_flow_entry* flows,
+                           uint64_t* count, void* scratch, uint64_t scratch_bytes, void* stream) {
+    if (zp_flow_aggregate_device(arena, offs, lens, records, n, &opts.get(), mask, flow_of, flows,
+                                 count, scratch, scratch_bytes, stream) < 0)
+        throw std::runtime_error(std::string("zp_flow_aggregate_device: ") + zp_last_error());
+}
+
 // Per-batch counters (zp_stats_device): adds into counts[ZP_STATS_COUNT].
 inline void stats_device(const zp_record* records, uint64_t n, uint64_t* counts, void* stream) {
     if (zp_stats_device(records, n, counts, stream) < 0)

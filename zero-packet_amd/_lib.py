@@ -60,6 +60,10 @@ def hip():
         _sig(lib, "zp_select_device", i32, [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp])
         _sig(lib, "zp_gather_frames_device", i32,
              [vp, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp])
+        _sig(lib, "zp_flow_scratch_bytes", u64, [u64, u64])
+        _sig(lib, "zp_flow_aggregate_device", i32,
+             [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp])
+        _sig(lib, "zp__flow_combine", i32, [i32])                     # measurement hook
         _sig(lib, "zp_stats_device", i32, [vp, u64, vp, vp])
         _sig(lib, "zp_probe_read_device", i32, [vp, u64, vp, vp])
         _sig(lib, "zp_probe_tiles_device", i32, [vp, u64, u64, vp, vp, vp, vp, vp])
