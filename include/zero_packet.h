@@ -851,6 +851,122 @@ int zp_flow_aggregate_device(const uint8_t* arena, const uint64_t* offs, const u
                              void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Persistent flow table: the same grouping, kept across batches.             */
+/*                                                                            */
+/* A flow table is two pieces of caller-owned device memory: a `table` block  */
+/* of zp_flow_table_bytes(max_flows) bytes (a 64-byte header and the hash     */
+/* slots) and `flows`, max_flows zp_flow_state entries. The options are fixed */
+/* when the table is initialised: every later call must pass the same         */
+/* key_flags, max_flows and hash_mask. The library allocates nothing, waits   */
+/* for nothing and reads nothing back: every call is enqueue-only on the      */
+/* caller's stream and captures into a graph. One table is used from one      */
+/* stream at a time.                                                          */
+/*                                                                            */
+/* Epoch. The header holds `epoch`, the number of updates completed (0 after  */
+/*   init). Update number E, counted from 0, stamps what it touches with E    */
+/*   (its low 32 bits) and its last launch writes epoch = E + 1. The counter  */
+/*   lives on the device, so a replayed graph advances it.                    */
+/* Update. Which frames are keyed, and their keys, are exactly                */
+/*   zp_flow_aggregate_device's (same rule, mask and key_flags). With F0 the  */
+/*   table's flow count before the call:                                      */
+/*   1. a keyed frame whose key is in the table belongs to that flow;         */
+/*   2. the remaining keyed frames are grouped among themselves; their R      */
+/*      distinct keys are ranked 0..R-1 in ascending order of their first     */
+/*      frame in this batch. New key r is ADMITTED as flow F0 + r when        */
+/*      F0 + r < max_flows and REFUSED otherwise: a refused key's frames get  */
+/*      ZP_FLOW_NONE, contribute to no entry, and nothing of the key enters   */
+/*      the table, so a full table stays valid;                               */
+/*   3. an admitted flow's entry is {key, first_epoch = last_epoch = E, 0s};  */
+/*   4. every keyed frame that is not refused adds 1 to its flow's packets    */
+/*      and lens[i] to its bytes, ORs its TCP flags in, and sets last_epoch   */
+/*      = E.                                                                  */
+/*   Every output byte is the same whatever order the hardware runs in.       */
+/* Retire. With E the header's epoch, flow f is retired when                  */
+/*   max_idle != ZP_FLOW_IDLE_NEVER and E - 1 - last_epoch >= max_idle (the   */
+/*   left side is the number of updates since the one that last saw the flow; */
+/*   0 retires everything), or when ZP_FLOW_STATE_TCP_FLAGS & tcp_any != 0.   */
+/*   Survivors are compacted stably to flows[0, F') byte for byte, so flows   */
+/*   stay numbered in order of first appearance.                              */
+/* ------------------------------------------------------------------------- */
+#define ZP_FLOW_IDLE_NEVER 0xFFFFFFFFu
+typedef struct zp_flow_state {       /* 64 bytes */
+    zp_flow_key key;                 /* as zp_flow_aggregate_device builds it                */
+    uint32_t first_epoch, last_epoch;/* the updates that admitted and last saw the flow      */
+    uint64_t packets_flags;          /* bits 0-55 packets, bits 56-63 OR of the TCP flags    */
+    uint64_t bytes;                  /* sum of lens                                          */
+} zp_flow_state;
+#define ZP_FLOW_STATE_PACKETS(e)   ((e).packets_flags & 0x00FFFFFFFFFFFFFFull)
+#define ZP_FLOW_STATE_TCP_FLAGS(e) ((uint8_t)((e).packets_flags >> 56))
+
+/* Bytes of the `table` block: a 64-byte header and one 4-byte slot for each of
+ * the first power of two >= 2 * max_flows slots (at least 64): at most 16 B per
+ * max_flows + 512 B. max_flows above 2^30 is refused by the calls. */
+uint64_t zp_flow_table_bytes(uint64_t max_flows);
+/* Device scratch of one update of n frames: zp_flow_aggregate_device's for n
+ * frames and n flows, at most 96 B per frame + 4,096 B. */
+uint64_t zp_flow_update_scratch_bytes(uint64_t n);
+/* Device scratch of a retire: a staging copy of the survivors and the ranking,
+ * at most 72 B per max_flows + 4,096 B. */
+uint64_t zp_flow_retire_scratch_bytes(uint64_t max_flows);
+
+/* Writes the table's header (a signature of `opts`, F = 0, epoch = 0) and
+ * empties the slots; `flows` is not touched. One launch. Refused (negative,
+ * zp_last_error names the cause): null opts or table, unknown key_flags bits,
+ * a nonzero pad, max_flows == 0 or above 2^30, a misaligned table (8 B),
+ * table_bytes below zp_flow_table_bytes(max_flows). */
+int zp_flow_table_init_device(void* table, uint64_t table_bytes, const zp_flow_opts* opts /* host */,
+                              void* stream);
+
+/* One update of the table by a parsed batch (the rule above).
+ *   flow_of  optional, n entries: the table-wide flow number, or ZP_FLOW_NONE
+ *            (not keyed, or refused);
+ *   count    required, 8 words: {F after the call, flows admitted, keyed frames,
+ *            keyed bytes, refused flows, refused frames, E, status}. Keyed frames
+ *            and bytes count every keyed frame, the refused ones included.
+ *            status is 1, and nothing else anywhere is written or changed, when
+ *            the header's signature does not match `opts`: a table never
+ *            initialised, or initialised with other options. Every kernel of
+ *            the call checks the signature first.
+ * n == 0 still completes an epoch and writes count. Scratch of any prior
+ * content gives the same result. Refused before anything is launched: what
+ * zp_flow_aggregate_device refuses, and a null or too small table, n >= 2^31,
+ * max_flows > 2^30, scratch_bytes below zp_flow_update_scratch_bytes(n), a
+ * misaligned pointer (table, count, mask: 8 B; flows: 16 B; flow_of: 4 B).
+ * Seven launches (key, find + insert, mark, scan, admit, label, finish; a
+ * second scan launch past ZP_SELECT_SCAN_FRAMES frames); one with n == 0. */
+int zp_flow_update_device(const uint8_t* arena, const uint64_t* offs, const uint32_t* lens,
+                          const zp_record* records, uint64_t n,
+                          const zp_flow_opts* opts /* host */, const uint64_t* mask /* optional */,
+                          void* table, uint64_t table_bytes,
+                          zp_flow_state* flows /* max_flows entries */,
+                          uint32_t* flow_of /* optional: n entries */,
+                          uint64_t* count /* required: 8 device words */,
+                          void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* Retires flows by the two predicates above (tcp_any: a mask of TCP flag bits,
+ * at most 0xFF; 0 for none).
+ *   retired  optional, max_flows entries: the retired entries in ascending old
+ *            number (the export record);
+ *   remap    optional, max_flows words: remap[f] for f below the old F is the
+ *            flow's new number, or ZP_FLOW_NONE; words past the old F are not
+ *            written;
+ *   count    required, 2 words: {F', flows retired}. On a signature mismatch
+ *            count[1] = UINT64_MAX and nothing else is written.
+ * The slots are rebuilt from the survivors, the header gets F = F', epoch is
+ * untouched, entries of `flows` at and past F' are left as they are. Refused
+ * before anything is launched: null opts, table, flows, count or scratch, bad
+ * opts as for init, tcp_any above 0xFF, a too small table or scratch (below
+ * zp_flow_retire_scratch_bytes(max_flows)), a misaligned pointer (table, count:
+ * 8 B; flows, retired: 16 B; remap: 4 B). Six launches (mark, scan, move,
+ * copy back + clear, re-insert, finish; a second scan launch past
+ * ZP_SELECT_SCAN_FRAMES flows). */
+int zp_flow_retire_device(const zp_flow_opts* opts /* host */, void* table, uint64_t table_bytes,
+                          zp_flow_state* flows, uint32_t max_idle, uint32_t tcp_any,
+                          zp_flow_state* retired /* optional */, uint32_t* remap /* optional */,
+                          uint64_t* count /* required: 2 device words */,
+                          void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Batched PacketBuilder. The reference builds one    */
 /* frame with a typestate chain over a caller-sized buffer                    */
 /* (builder.rs:55-909): PacketBuilder::new(&mut buf).ethernet(..).ipv4(..)    */

@@ -742,6 +742,54 @@ inline void flow_aggregate(const uint8_t* arena, const uint64_t* offs, const uin
         throw std::runtime_error(std::string("zp_flow_aggregate_device: ") + zp_last_error());
 }
 
+// A flow table that persists across batches (zp_flow_table_init_device,
+// zp_flow_update_device, zp_flow_retire_device; zero_packet.h has the rule).
+// A thin view: the caller owns `table` (zp::FlowTable::table_bytes(opts)
+// bytes) and `flows` (opts.max_flows entries) on the device; every call is
+// enqueue-only on `stream`, and a refusal throws with zp_last_error's text.
+//   zp::FlowTable t(zp::FlowOpts(1 << 20), d_table, nbytes, d_flows);
+//   t.init(stream);
+//   t.update(arena, offs, lens, recs, n, nullptr, d_flow_of, d_count8, scratch, nscratch, stream);
+//   t.retire(8, 0x05, d_retired, d_remap, d_count2, scratch, nscratch, stream);
+class FlowTable {
+public:
+    FlowTable(const FlowOpts& opts, void* table, uint64_t table_bytes, zp_flow_state* flows)
+        : o_(opts), table_(table), bytes_(table_bytes), flows_(flows) {}
+    static uint64_t table_bytes(const FlowOpts& opts) { return zp_flow_table_bytes(opts.get().max_flows); }
+    static uint64_t update_scratch_bytes(uint64_t n) { return zp_flow_update_scratch_bytes(n); }
+    uint64_t retire_scratch_bytes() const { return zp_flow_retire_scratch_bytes(o_.get().max_flows); }
+    const FlowOpts& opts() const { return o_; }
+    zp_flow_state* flows() const { return flows_; }
+
+    // F = 0, epoch = 0, the slots emptied; `flows` is not touched.
+    void init(void* stream) {
+        if (zp_flow_table_init_device(table_, bytes_, &o_.get(), stream) < 0)
+            throw std::runtime_error(std::string("zp_flow_table_init_device: ") + zp_last_error());
+    }
+    // count: 8 device words {F, admitted, keyed frames, keyed bytes, refused
+    // flows, refused frames, epoch, status}.
+    void update(const uint8_t* arena, const uint64_t* offs, const uint32_t* lens,
+                const zp_record* records, uint64_t n, const uint64_t* mask, uint32_t* flow_of,
+                uint64_t* count, void* scratch, uint64_t scratch_bytes, void* stream) {
+        if (zp_flow_update_device(arena, offs, lens, records, n, &o_.get(), mask, table_, bytes_, flows_,
+                                  flow_of, count, scratch, scratch_bytes, stream) < 0)
+            throw std::runtime_error(std::string("zp_flow_update_device: ") + zp_last_error());
+    }
+    // count: 2 device words {F', flows retired}. max_idle: ZP_FLOW_IDLE_NEVER for no age limit.
+    void retire(uint32_t max_idle, uint32_t tcp_any, zp_flow_state* retired, uint32_t* remap,
+                uint64_t* count, void* scratch, uint64_t scratch_bytes, void* stream) {
+        if (zp_flow_retire_device(&o_.get(), table_, bytes_, flows_, max_idle, tcp_any, retired, remap,
+                                  count, scratch, scratch_bytes, stream) < 0)
+            throw std::runtime_error(std::string("zp_flow_retire_device: ") + zp_last_error());
+    }
+
+private:
+    FlowOpts o_;
+    void* table_;
+    uint64_t bytes_;
+    zp_flow_state* flows_;
+};
+
 // Per-batch counters (zp_stats_device): adds into counts[ZP_STATS_COUNT].
 inline void stats_device(const zp_record* records, uint64_t n, uint64_t* counts, void* stream) {
     if (zp_stats_device(records, n, counts, stream) < 0)

@@ -64,6 +64,14 @@ def hip():
         _sig(lib, "zp_flow_aggregate_device", i32,
              [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp])
         _sig(lib, "zp__flow_combine", i32, [i32])                     # measurement hook
+        _sig(lib, "zp_flow_table_bytes", u64, [u64])
+        _sig(lib, "zp_flow_update_scratch_bytes", u64, [u64])
+        _sig(lib, "zp_flow_retire_scratch_bytes", u64, [u64])
+        _sig(lib, "zp_flow_table_init_device", i32, [vp, u64, vp, vp])
+        _sig(lib, "zp_flow_update_device", i32,
+             [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp])
+        _sig(lib, "zp_flow_retire_device", i32,
+             [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp, u64, vp])
         _sig(lib, "zp_stats_device", i32, [vp, u64, vp, vp])
         _sig(lib, "zp_probe_read_device", i32, [vp, u64, vp, vp])
         _sig(lib, "zp_probe_tiles_device", i32, [vp, u64, u64, vp, vp, vp, vp, vp])
