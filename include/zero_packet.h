@@ -758,6 +758,84 @@ int zp_gather_frames_device(const uint8_t* arena, const uint64_t* offs, const ui
                             void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Classify: a first-match rule table over parsed frames. A rule is exactly a */
+/* zp_select: frame i matches rule r exactly when zp_select_device with       */
+/* rules[r] would select it (the all-zero value of a column whose reader is   */
+/* absent or whose record holds an error included). A table holds nrules      */
+/* rules in priority order, 1 <= nrules <= ZP_CLASSIFY_MAX_RULES:             */
+/*   rule_of[i]  the smallest r whose rule matches frame i, or ZP_RULE_NONE;  */
+/*   hits        nrules + 1 entries: frame i ADDS 1 and lens[i] to entry      */
+/*               rule_of[i], an unmatched frame to entry nrules. The call     */
+/*               adds to what hits holds (the caller zeroes it once), so the  */
+/*               counters persist across batches and graph replays; integer   */
+/*               adds make them independent of the execution order;           */
+/*   mask        the words zp_select_device writes (bit i % 64 of word i /    */
+/*               64, bits at and past n zero): frame i's bit is set when bit  */
+/*               rule_of[i] of `accept` is set, bit nrules standing for "no   */
+/*               rule". accept: a host bitmap of nrules + 1 bits in           */
+/*               ceil((nrules + 1) / 64) words; NULL = "matched any rule".    */
+/*               zp_flow_aggregate_device / zp_flow_update_device take it.    */
+/* ------------------------------------------------------------------------- */
+#define ZP_CLASSIFY_MAX_RULES 256
+#define ZP_RULE_NONE 0xFFFFFFFFu
+typedef struct zp_rule_hits { uint64_t packets, bytes; } zp_rule_hits;
+
+/* Bytes of the compiled form of an nrules table (non-decreasing in nrules; 0
+ * for an nrules out of range). */
+uint64_t zp_classify_table_bytes(uint32_t nrules);
+
+/* Compiles rules[0, nrules) into `table` (host memory, 4-byte aligned,
+ * table_bytes >= zp_classify_table_bytes(nrules)): a private, versioned form
+ * the caller copies to the device as it is; the library allocates no device
+ * memory and this call touches no device. Identical terms and identical
+ * record predicates of different rules are stored once. The same rules give
+ * the same zp_classify_table_bytes(nrules) bytes (padding is zero), so tables
+ * can be compared and cached.
+ * Returns 1 when some rule has terms (the table reads frames), 0 when none
+ * has (a record-only table): this is how the host learns what it has to pass
+ * to zp_classify_device, which cannot see the device copy.
+ * Refused with a negative value, `table` untouched and zp_last_error naming
+ * the rule index and the cause: everything zp_select_device refuses of a
+ * selector (nterms > ZP_SELECT_MAX_TERMS, a column out of range, a nonzero
+ * pad, an unknown op, RANGE / NOT_RANGE on a byte-array column); also nrules
+ * == 0 or > ZP_CLASSIFY_MAX_RULES, a null pointer, a table_bytes too small. */
+int zp_classify_compile(const zp_select* rules, uint32_t nrules,
+                        void* table /* host */, uint64_t table_bytes);
+
+/* Classifies a parsed batch: one launch on `stream`, nothing allocated,
+ * nothing waits, so the call captures into a graph. `table` is the device
+ * copy of what zp_classify_compile wrote for the same nrules; `accept` is
+ * host memory; everything else device memory.
+ * Which frames are read. arena == NULL and offs == NULL is the caller's claim
+ * that the table is record-only (zp_classify_compile returned 0): records and
+ * lens are streamed and no frame is read; lens may then be NULL too when
+ * hits is NULL and no rule bounds the length. A table that reads frames
+ * (compile returned 1) needs arena, offs and lens. A record-only table may
+ * also be given with all three; it is then evaluated without reading a frame.
+ * status (required, one device word). The kernel first checks the table
+ * header's signature, version and nrules, and the claims above (record-only
+ * against a table with terms; no lens against a table with length bounds).
+ * On a mismatch it writes status = 1 and nothing else anywhere, and reads
+ * nothing of the table behind the header: a table compiled for another count,
+ * one never written. Otherwise status = 0. n == 0 writes status only.
+ * Every rule_of[i], i < n, is written and nothing at or past n; mask words
+ * [0, ceil(n / 64)); hits entries are only added to (one 64-bit atomic add
+ * per workgroup and non-zero entry).
+ * Refused with a negative value before any HIP call (zp_last_error names the
+ * cause): a null records, table or status; nrules out of range; table_bytes
+ * below zp_classify_table_bytes(nrules); n >= 2^32; table, hits, mask or
+ * status not 8-byte aligned, rule_of not 4-byte aligned; hits without lens;
+ * one of arena / offs given without the other or without lens. */
+int zp_classify_device(const uint8_t* arena, const uint64_t* offs, const uint32_t* lens,
+                       const zp_record* records, uint64_t n,
+                       const void* table /* device copy of the compiled table */,
+                       uint64_t table_bytes, uint32_t nrules,
+                       const uint64_t* accept /* host, optional */,
+                       uint32_t* rule_of /* optional, n */, zp_rule_hits* hits /* optional, nrules+1 */,
+                       uint64_t* mask /* optional, ceil(n/64) */,
+                       uint64_t* status /* required, 1 device word */, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Flow table: group parsed frames by key on the device, with per-flow        */
 /* counters. zp_stats_device counts per batch; this counts per key.           */
 /*                                                                            */

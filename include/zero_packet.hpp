@@ -705,6 +705,51 @@ inline void gather_frames(const uint8_t* arena, const uint64_t* offs, const uint
         throw std::runtime_error(std::string("zp_gather_frames_device: ") + zp_last_error());
 }
 
+// A first-match rule table for zp::classify (zp_classify_compile,
+// zero_packet.h): built from selectors in priority order, it owns the
+// host-compiled bytes; the caller copies data() (bytes() of them, to memory
+// aligned to 8 bytes) to the device and passes that copy to zp::classify.
+//   zp::RuleTable table({zp::Select().ok().eq(ZP_COL_L4_PROTO, 6), zp::Select().ok(false)});
+// A refused rule throws with zp_last_error's text (it names the rule).
+class RuleTable {
+public:
+    explicit RuleTable(const std::vector<Select>& rules) : nrules_((uint32_t)rules.size()) {
+        std::vector<zp_select> enc;
+        enc.reserve(rules.size());
+        for (const Select& r : rules) enc.push_back(r.get());
+        bytes_.resize((size_t)(zp_classify_table_bytes(nrules_) / 8));   // 0 for a count out of range
+        const int rc = zp_classify_compile(enc.data(), nrules_, bytes_.data(), 8 * bytes_.size());
+        if (rc < 0) throw std::invalid_argument(std::string("zp_classify_compile: ") + zp_last_error());
+        needs_frames_ = rc != 0;
+    }
+    const void* data() const { return bytes_.data(); }
+    uint64_t bytes() const { return 8 * (uint64_t)bytes_.size(); }
+    uint32_t nrules() const { return nrules_; }
+    // Whether some rule has terms: the table then needs arena, offs and lens;
+    // a record-only table is given with arena == offs == nullptr.
+    bool needs_frames() const { return needs_frames_; }
+
+private:
+    std::vector<uint64_t> bytes_;
+    uint32_t nrules_;
+    bool needs_frames_ = false;
+};
+
+// zp_classify_device (zero_packet.h): enqueue-only on `stream`; a refusal
+// throws with zp_last_error's text. device_table: the device copy of
+// table.data(). A record-only table never reads arena / offs: they are passed
+// on as nullptr. accept: host bitmap of nrules + 1 bits, or nullptr.
+inline void classify(const uint8_t* arena, const uint64_t* offs, const uint32_t* lens,
+                     const zp_record* records, uint64_t n, const RuleTable& table,
+                     const void* device_table, const uint64_t* accept, uint32_t* rule_of,
+                     zp_rule_hits* hits, uint64_t* mask, uint64_t* status, void* stream) {
+    const bool f = table.needs_frames();
+    if (zp_classify_device(f ? arena : nullptr, f ? offs : nullptr, lens, records, n, device_table,
+                           table.bytes(), table.nrules(), accept, rule_of, hits, mask, status,
+                           stream) < 0)
+        throw std::runtime_error(std::string("zp_classify_device: ") + zp_last_error());
+}
+
 // Options for zp::flow_aggregate (zp_flow_opts, zero_packet.h): the 5-tuple
 // unless told otherwise.
 //   zp::FlowOpts(max_flows).vlan().bidir()

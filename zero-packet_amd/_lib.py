@@ -60,6 +60,10 @@ def hip():
         _sig(lib, "zp_select_device", i32, [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp])
         _sig(lib, "zp_gather_frames_device", i32,
              [vp, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp])
+        _sig(lib, "zp_classify_table_bytes", u64, [u32])
+        _sig(lib, "zp_classify_compile", i32, [vp, u32, vp, u64])
+        _sig(lib, "zp_classify_device", i32,
+             [vp, vp, vp, vp, u64, vp, u64, u32, vp, vp, vp, vp, vp, vp])
         _sig(lib, "zp_flow_scratch_bytes", u64, [u64, u64])
         _sig(lib, "zp_flow_aggregate_device", i32,
              [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp])
