@@ -836,6 +836,97 @@ int zp_classify_device(const uint8_t* arena, const uint64_t* offs, const uint32_
                        uint64_t* status /* required, 1 device word */, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Route: longest-prefix match of a frame's address against a table of up to  */
+/* ZP_ROUTE_MAX_PREFIXES prefixes (a forwarding table, a blocklist).          */
+/*                                                                            */
+/* Routed frames. Frame i is looked up when its record has err == 0 and an    */
+/*   outer IPv4 or IPv6 reader, and, if `only` (the words zp_select_device    */
+/*   writes) is given, bit i % 64 of only[i / 64] is set. Every other frame   */
+/*   gets ZP_ROUTE_NONE. The address and its version are exactly the entries  */
+/*   zp_extract_columns_device would store for `col` (ZP_COL_DEST_ADDR or     */
+/*   ZP_COL_SRC_ADDR) and for ZP_COL_IP_VERSION: under IP-in-IP the outer     */
+/*   header's.                                                                */
+/* Result. value_of[i] is the `value` of the longest prefix of the frame's    */
+/*   version whose first `len` bits equal the address's, ZP_ROUTE_NONE when   */
+/*   no prefix matches. The version is part of the match: 10.0.0.1 never      */
+/*   matches the IPv6 prefix 0a00:1::/32, and a default route (len 0) of      */
+/*   version 4 does not cover IPv6 frames.                                    */
+/* Mask. The words zp_select_device writes (bit i % 64 of word i / 64, bits   */
+/*   at and past n zero): frame i's bit is set when value_of[i] is not        */
+/*   ZP_ROUTE_NONE. zp_select_device's consumers and both flow entry points   */
+/*   take it. `mask` and `only` must not overlap.                             */
+/* ------------------------------------------------------------------------- */
+#define ZP_ROUTE_NONE         0xFFFFFFFFu
+#define ZP_ROUTE_VALUE_MAX    0x7FFFFFFEu
+#define ZP_ROUTE_MAX_PREFIXES (1u << 20)
+typedef struct zp_route_prefix {   /* 24 bytes */
+    uint8_t  addr[16];  /* as the address columns hold it: IPv4 in bytes 0-3, zeros behind */
+    uint8_t  len;       /* 0..32 for version 4, 0..128 for version 6; 0 = default route */
+    uint8_t  version;   /* 4 or 6 */
+    uint8_t  pad[2];    /* must be 0 */
+    uint32_t value;     /* caller's next hop / class id, <= ZP_ROUTE_VALUE_MAX */
+} zp_route_prefix;
+
+/* Exact bytes of the compiled form of p[0, n) (host; n == 0: the empty table,
+ * p may be NULL); 0 when zp_route_compile would refuse the prefixes
+ * (zp_last_error names the cause). The form is a leaf-pushed multibit trie:
+ * one root of 65,536 dword entries per version, then 1-KiB nodes of 256
+ * entries, so IPv4 is answered after at most 3 dependent loads and IPv6
+ * after at most 15. The size is at most
+ *   64 + 512 KiB + 1 KiB * sum over the prefixes of max(0, ceil((len - 16) / 8))
+ * bytes (prefixes that share leading bytes share nodes); the caller decides
+ * whether that fits. */
+uint64_t zp_route_table_bytes(const zp_route_prefix* p, uint32_t n);
+
+/* Compiles p[0, n) into `table` (host memory, 4-byte aligned, table_bytes >=
+ * zp_route_table_bytes(p, n)): a private, versioned form the caller copies to
+ * the device as it is; the library allocates no device memory and this call
+ * touches no device. The same set of prefixes in any order gives the same
+ * zp_route_table_bytes(p, n) bytes (padding is zero; nothing behind them is
+ * written), so tables can be compared and cached. n == 0 is the empty table:
+ * everything routes to ZP_ROUTE_NONE. Returns 0.
+ * Refused with a negative value, `table` untouched and zp_last_error naming
+ * the prefix index and the cause: n above ZP_ROUTE_MAX_PREFIXES; a version
+ * other than 4 or 6; a len past the version's width; a nonzero pad; a value
+ * above ZP_ROUTE_VALUE_MAX; address bits set past len (for version 4 also
+ * past byte 3); two prefixes with the same (version, len, addr), both
+ * indices named; a null pointer; a misaligned table; a table_bytes too small. */
+int zp_route_compile(const zp_route_prefix* p, uint32_t n, void* table /* host */,
+                     uint64_t table_bytes);
+
+/* One address through a compiled table on the host: the walk the kernel
+ * runs. table_bytes is the table's own size (zp_route_table_bytes); addr as
+ * in zp_route_prefix (version 4 reads bytes 0-3). ZP_ROUTE_NONE for a table
+ * whose header does not say that, and for a version other than 4 or 6.
+ * Whatever the bytes behind a valid header hold, the walk makes at most 3
+ * (version 4) or 15 (version 6) loads, all inside [table, table + table_bytes). */
+uint32_t zp_route_lookup_host(const void* table, uint64_t table_bytes, const uint8_t addr[16],
+                              int version);
+
+/* Routes a parsed batch: one launch on `stream`, nothing allocated, nothing
+ * waits, so the call captures into a graph. `table` is the device copy of
+ * what zp_route_compile wrote and table_bytes its size
+ * (zp_route_table_bytes); everything else is device memory too.
+ * status (required, one device word). The kernel first checks the table
+ * header: signature, version, and the byte size against table_bytes. On a
+ * mismatch it writes status = 1 and nothing else anywhere, and reads nothing
+ * of the table behind the header. Otherwise status = 0. n == 0 writes status
+ * only. Every value_of[i], i < n, is written and nothing at or past n; mask
+ * words [0, ceil(n / 64)).
+ * Refused with a negative value before any HIP call (zp_last_error names the
+ * cause): a null records, table or status; col not ZP_COL_DEST_ADDR or
+ * ZP_COL_SRC_ADDR; arena, offs or lens missing; n >= 2^32; a table_bytes
+ * below an empty table's; table, only, mask or status not 8-byte aligned,
+ * value_of not 4-byte aligned; mask overlapping only. */
+int zp_route_device(const uint8_t* arena, const uint64_t* offs, const uint32_t* lens,
+                    const zp_record* records, uint64_t n,
+                    const void* table /* device copy of the compiled table */, uint64_t table_bytes,
+                    int col /* ZP_COL_DEST_ADDR or ZP_COL_SRC_ADDR */,
+                    const uint64_t* only /* optional, select's mask words */,
+                    uint32_t* value_of /* optional, n */, uint64_t* mask /* optional, ceil(n/64) */,
+                    uint64_t* status /* required, 1 device word */, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Flow table: group parsed frames by key on the device, with per-flow        */
 /* counters. zp_stats_device counts per batch; this counts per key.           */
 /*                                                                            */

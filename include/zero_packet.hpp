@@ -750,6 +750,67 @@ inline void classify(const uint8_t* arena, const uint64_t* offs, const uint32_t*
         throw std::runtime_error(std::string("zp_classify_device: ") + zp_last_error());
 }
 
+// A longest-prefix-match table for zp::route (zp_route_compile,
+// zero_packet.h): built from prefixes in any order, it owns the host-compiled
+// bytes; the caller copies data() (bytes() of them, to memory aligned to 8
+// bytes) to the device and passes that copy to zp::route.
+//   zp::RouteTable table({zp::RouteTable::v4({10, 0, 0, 0}, 8, 1),
+//                         zp::RouteTable::v6({0x20, 0x01, 0x0d, 0xb8}, 32, 2)});
+//   table.lookup({10, 1, 2, 3});     // 1: the kernel's walk, on the host
+// A refused prefix throws with zp_last_error's text (it names the prefix).
+class RouteTable {
+public:
+    static zp_route_prefix v4(const std::array<uint8_t, 4>& addr, uint8_t len, uint32_t value) {
+        zp_route_prefix p{};
+        std::memcpy(p.addr, addr.data(), 4);
+        p.len = len;
+        p.version = 4;
+        p.value = value;
+        return p;
+    }
+    static zp_route_prefix v6(const std::array<uint8_t, 16>& addr, uint8_t len, uint32_t value) {
+        zp_route_prefix p{};
+        std::memcpy(p.addr, addr.data(), 16);
+        p.len = len;
+        p.version = 6;
+        p.value = value;
+        return p;
+    }
+    explicit RouteTable(const std::vector<zp_route_prefix>& prefixes) {
+        const uint32_t n = (uint32_t)prefixes.size();
+        const uint64_t bytes = zp_route_table_bytes(prefixes.data(), n);
+        if (bytes == 0) throw std::invalid_argument(std::string("zp_route_table_bytes: ") + zp_last_error());
+        bytes_.resize((size_t)(bytes / 8));
+        if (zp_route_compile(prefixes.data(), n, bytes_.data(), bytes) < 0)
+            throw std::invalid_argument(std::string("zp_route_compile: ") + zp_last_error());
+    }
+    const void* data() const { return bytes_.data(); }
+    uint64_t bytes() const { return 8 * (uint64_t)bytes_.size(); }
+    // The value of the longest prefix that matches, ZP_ROUTE_NONE if none.
+    uint32_t lookup(const std::array<uint8_t, 4>& addr) const {
+        uint8_t a[16] = {addr[0], addr[1], addr[2], addr[3]};
+        return zp_route_lookup_host(data(), bytes(), a, 4);
+    }
+    uint32_t lookup(const std::array<uint8_t, 16>& addr) const {
+        return zp_route_lookup_host(data(), bytes(), addr.data(), 6);
+    }
+
+private:
+    std::vector<uint64_t> bytes_;
+};
+
+// zp_route_device (zero_packet.h): enqueue-only on `stream`; a refusal throws
+// with zp_last_error's text. device_table: the device copy of table.data().
+// col: ZP_COL_DEST_ADDR or ZP_COL_SRC_ADDR; only: select's mask words or nullptr.
+inline void route(const uint8_t* arena, const uint64_t* offs, const uint32_t* lens,
+                  const zp_record* records, uint64_t n, const RouteTable& table,
+                  const void* device_table, int col, const uint64_t* only, uint32_t* value_of,
+                  uint64_t* mask, uint64_t* status, void* stream) {
+    if (zp_route_device(arena, offs, lens, records, n, device_table, table.bytes(), col, only,
+                        value_of, mask, status, stream) < 0)
+        throw std::runtime_error(std::string("zp_route_device: ") + zp_last_error());
+}
+
 // Options for zp::flow_aggregate (zp_flow_opts, zero_packet.h): the 5-tuple
 // unless told otherwise.
 //   zp::FlowOpts(max_flows).vlan().bidir()

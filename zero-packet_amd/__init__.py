@@ -8,6 +8,7 @@ Import with importlib (the directory name has a hyphen):
   zp.columns.extract(arena, offs, lens, recs) reader getters as SoA device columns
   zp.select.run / gather(...)                filter parsed frames on the device into a sub-batch
   zp.classify.RuleTable(rules, device).run(...) first-match rule table: rule_of, per-rule counters, mask
+  zp.routes.RouteTable(prefixes, device).run(...) longest-prefix match of an address: value_of, mask
   zp.flows.aggregate(arena, offs, lens, recs) group parsed frames by 5-tuple: flow table on the device
   zp.stats.count(recs)                       per-protocol / per-error counters (device)
   zp.ring.Ring(device, slots, slot_bytes)    host-ring ingestion (H2D/parse/D2H in flight)
@@ -25,8 +26,8 @@ from .parser import (ArpReader, AuthenticationHeaderReader, EthernetReader,  # n
                      internet_checksum, pseudo_header, verify_internet_checksum)
 
 try:  # torch-dependent batch API
-    from . import batch, builder, classify, columns, flows, select, stats  # noqa: F401
+    from . import batch, builder, classify, columns, flows, routes, select, stats  # noqa: F401
 except ImportError:  # pragma: no cover
-    batch = builder = classify = columns = flows = select = stats = None
+    batch = builder = classify = columns = flows = routes = select = stats = None
 
 __all__ = ["PacketParser", "ZeroPacketError", "batch", "records"]

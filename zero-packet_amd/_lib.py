@@ -64,6 +64,10 @@ def hip():
         _sig(lib, "zp_classify_compile", i32, [vp, u32, vp, u64])
         _sig(lib, "zp_classify_device", i32,
              [vp, vp, vp, vp, u64, vp, u64, u32, vp, vp, vp, vp, vp, vp])
+        _sig(lib, "zp_route_table_bytes", u64, [vp, u32])
+        _sig(lib, "zp_route_compile", i32, [vp, u32, vp, u64])
+        _sig(lib, "zp_route_lookup_host", u32, [vp, u64, vp, i32])
+        _sig(lib, "zp_route_device", i32, [vp, vp, vp, vp, u64, vp, u64, i32, vp, vp, vp, vp, vp])
         _sig(lib, "zp_flow_scratch_bytes", u64, [u64, u64])
         _sig(lib, "zp_flow_aggregate_device", i32,
              [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp])
