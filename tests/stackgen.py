@@ -12,6 +12,9 @@ the way the reference builder does. On top of it:
                       the end of the parse window (112 B from the frame's
                       16-B aligned start)
   place_aligned()     each frame at each of the 16 start alignments mod 16
+  short_tail_families()  the same stacks without payload: frames that end
+                      before the bytes a column reader asks for
+  with_filler()       an arena with the bytes between its frames set
 """
 import numpy as np
 
@@ -246,6 +249,70 @@ def window_families(rng):
                 for l4 in ("tcp", "udp", icmp(inner)):
                     c.append(stack(rng, eth_len, [("v6", [(0, h)]), inner], l4, min_payload=24))
     return {"A": a, "B": b, "C": c}
+
+
+def bare_stack(rng, eth_len, levels, l4):
+    """stack() without payload: the frame ends at the last byte of its L4
+    header (8 B of UDP / ICMP), for l4 "none" at the last byte of its
+    innermost IP header. The reference rejects a frame under 64 B
+    (ethernet.rs: the minimum frame size), so a shorter stack gets the
+    payload that brings it to 64 B, the smallest it accepts."""
+    size = max(64, eth_len + L4_MIN[l4] + sum(
+        lv[1] * 4 if lv[0] == "v4" else 40 + sum(s for _, s in lv[1]) for lv in levels))
+    f = ethernet(rng, eth_len, 0x0800 if levels[0][0] == "v4" else 0x86DD)
+    left = size - eth_len
+    for k, lv in enumerate(levels):
+        nxt = L4_PROTO[l4] if k + 1 == len(levels) else (4 if levels[k + 1][0] == "v4" else 41)
+        if lv[0] == "v4":
+            left -= lv[1] * 4
+            f += ipv4(rng, lv[1], nxt, left)
+        else:
+            chain = lv[1]
+            left -= 40
+            f += ipv6(rng, chain[0][0] if chain else nxt, left)
+            for j, (_, s) in enumerate(chain):
+                f += options(rng, chain[j + 1][0] if j + 1 < len(chain) else nxt, s)
+                left -= s
+    f += l4_segment(rng, l4, left)
+    assert len(f) == size and (left == L4_MIN[l4] or size == 64)
+    return repair(bytes(f))
+
+
+def short_tail_families(rng):
+    """{"A" | "B" | "C": frames}: the stacks of window_families() as
+    bare_stack() frames, so that every frame is shorter than the bytes a
+    column reader asks for (l4 + 20, inner + 40 or l3 + 40) and its header
+    window ends with the frame. L4: UDP and ICMP (8 B, where a TCP header
+    would have 20), and "none" where the innermost IP header is an IPv4 one:
+    that frame ends 20 B into the 40 a reader asks for (behind an IPv6 header
+    without L4 nothing is missing, so those stacks are left out)."""
+    inners = (("v4", 5), ("v6", []), ("v6", [(60, 16)]))
+    kinds = lambda lv: ("udp", "icmpv4", "none") if lv[0] == "v4" else ("udp", "icmpv6")
+    a, b, c = [], [], []
+    for eth_len in ETH_LENS:
+        for e in range(0, 88, 8):
+            for l4 in ("udp", "icmpv6"):
+                a.append(bare_stack(rng, eth_len, [("v6", [(0, e)] if e else [])], l4))
+        outers = [("v4", ihl) for ihl in range(5, 16, 2)] + [("v6", [])]
+        for outer in outers:
+            for inner in inners:
+                for l4 in kinds(inner):
+                    b.append(bare_stack(rng, eth_len, [outer, inner], l4))
+        for h in range(16, 64, 8):
+            for inner in inners:
+                for l4 in kinds(inner):
+                    c.append(bare_stack(rng, eth_len, [("v6", [(0, h)]), inner], l4))
+    return {"A": a, "B": b, "C": c}
+
+
+def with_filler(arena, offs, lens, fill):
+    """A copy of the arena with every byte that belongs to no frame set to `fill`."""
+    own = np.zeros(len(arena), bool)
+    for o, n in zip(offs, lens):
+        own[int(o):int(o) + int(n)] = True
+    out = arena.copy()
+    out[~own] = fill
+    return out
 
 
 def place_aligned(frames):

@@ -2,8 +2,12 @@
 // the 8-B zp_record unpacked into zp_rec_full (both forms, inline chains),
 // the header bytes to stage for it, and the fields the record does not carry
 // (final_next_header, the far-L4 form's eth_len / inner_off) read from the
-// staged frame. Shared by zp_columns_kernel (zp_fields.hip) and the term
-// instantiation of zp_select_mark_kernel (zp_select.hip).
+// staged frame. Shared by every kernel that reads columns through the window:
+// zp_columns_kernel (zp_fields.hip), zp_select_mark_terms_kernel
+// (zp_select.hip), zp_classify_kernel (zp_classify.hip), zp_route_kernel
+// (zp_route.hip) and both instances of zp_flow_key_kernel (zp_flow.hip). Each
+// asks fx_rec_need() for its own column groups, so the same frame's window
+// ends elsewhere in each of them (tests/test_window_stages.py).
 #pragma once
 #include "zp_cols.h"
 #include "zp_win.h"
